@@ -17,7 +17,11 @@ Modes (BASELINE.json `configs`):
       with the backward) + fused AdamW on dyscene.yaml shapes (12 frames, 4096 points, 224x224), --batch per GPU (8 / 32).
   frame-parallel (configs[4], c5): one 256-frame clip, frames sharded over the ranks with exact single-GPU semantics
       (K/V all-gather per global block).  Strong scaling; at N = 1 the whole clip runs on one GPU.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+the headline; `--full` adds everything else the line can carry (`roofline` from an instrumented eager pass, `cpu_baseline`,
+the sustained rate, two clips in flight, the decoder-block replay and the `secondary` configurations).
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64, at most
+DUMP_BUDGET_BYTES in all), so that two builds can be compared output for output on the same seeded inputs.
 """
 from __future__ import annotations
 
@@ -41,6 +45,7 @@ PEAK_HBM_GBS = 8000.0
 PROFILE_ROUND = "r06"          # profiles/<round>_* hold the rocprofv3 summaries the roofline rows are checked against
 
 WORKLOAD = dict(B=1, T=32, N=2048, S=4096, HW=512, frames=32)   # BASELINE.json configs[1]
+DUMP_BUDGET_BYTES = 60 * 2 ** 20                                # --dump-outputs: all arrays together stay under 64 MB
 
 
 def algorithmic_flops(B, T, N, S, d=768, K=64, g=16, n_layer=16, pcd_layers=4, dino_depth=12):
@@ -64,10 +69,17 @@ def algorithmic_flops(B, T, N, S, d=768, K=64, g=16, n_layer=16, pcd_layers=4, d
 
 def build_model(device, frames, train=False):
     import motion324_amd as m
+    from concurrent.futures import ThreadPoolExecutor
     from motion324_amd import synth
     cfg = synth.make_config(frames=frames)
     model = m.Motion_Latent_Model(cfg)
-    sd = {k: torch.from_numpy(v) for k, v in synth.synth_state_dict(synth.Dims(frames=frames), seed=0).items()}
+    # synth.synth_state_dict tensor by tensor on a few threads (numpy drops the GIL in its array arithmetic): every tensor is
+    # its own counter-based stream, so the values are the same; ~250 M parameters otherwise cost most of a plain run's set-up.
+    # At most 16 threads: a shared host's full core count is not this process's
+    spec = synth.state_dict_spec(synth.Dims(frames=frames))
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex:
+        arrays = ex.map(lambda kv: synth.synth_tensor(0, kv[0], kv[1][0], kv[1][1]), spec.items())
+        sd = {k: torch.from_numpy(v) for k, v in zip(spec, arrays)}
     model.load_state_dict(sd, strict=False)
     model = (model.train() if train else model.eval()).to(device)
     model.auto_graph = False              # the bench drives its graphs and its eager (instrumented) passes explicitly
@@ -253,6 +265,23 @@ def sustained(dist_: Dist, step, seconds: float):
     return n, dt
 
 
+def dump_outputs(path: str, arrays) -> None:
+    """--dump-outputs: {name: tensor} -> <path>/<name>.npy in float32 (float64 stays float64).  An array larger than its
+    share of DUMP_BUDGET_BYTES is replaced by a fixed sample of its flattened elements (seeded index draw, the same on every
+    run of the same shapes), so that two builds of the project can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (share // t.element_size(),), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 # ----------------------------------------------------------------------------------------------- roofline rows
 def roofline_rows(rec, steps: int):
     """Per-symbol rows from the HIP-event recorder: (kernel template + grid) -> launches, avg us, algorithmic FLOP / bytes
@@ -408,7 +437,7 @@ def decoder_block_replay(model, sample, steps: int, q_mode: str = "pair"):
 
 
 def secondary_measurements(args, D, model, sd, sample, sample_np, ref_out, headline_ms=None):
-    """BASELINE's other configurations and the headline's precision variants, driver-visible in the default command
+    """BASELINE's other configurations and the headline's precision variants, in the --full line
     (each a few steps; a failure is reported in place, never raised): the headline without its two narrower-than-reference
     shortcuts, fp32 parity mode on c2, the c3 training step, the 256-frame clip on one GPU, and the PCIe hand-over."""
     import gc
@@ -707,11 +736,14 @@ def run_infer(args, D: Dist):
         step()
     dt, t_enq = timed(D, step, args.steps)
     out = last[0]
-    sus = sustained(D, step, args.sustain)
+    if args.dump_outputs and rank == 0:            # what the caller of a step receives: this rank's clip (N > 1: every rank's)
+        dump_outputs(args.dump_outputs, dict(pcd_moved=out, **({"pcd_moved_all_ranks": gathered[0]} if world > 1 else {})))
+    # everything below up to the result line is --full only: measurements of their own after the timed region
+    sus = sustained(D, step, args.sustain) if args.full else None
     # serving-throughput variant (reported next to the headline, never instead of it): two clips in flight -- consecutive
     # steps alternate between two streams / graphs, so one clip's kernels fill the partly filled last rounds of the other's
     two = None
-    if world == 1 and fast is not None and len(lanes) == 1 and not args.no_two_in_flight:
+    if args.full and world == 1 and fast is not None and len(lanes) == 1 and not args.no_two_in_flight:
         single = list(lanes)
         lanes[:] = [(torch.cuda.Stream(), fast), (torch.cuda.Stream(), m.GraphedForward(model))]
         for _ in range(4):
@@ -722,7 +754,7 @@ def run_infer(args, D: Dist):
         torch.cuda.synchronize()
         lanes[:] = single
     blk_replay = None
-    if world == 1 and fast is not None:
+    if args.full and world == 1 and fast is not None:
         try:
             blk_replay = decoder_block_replay(model, sample, args.steps)
             # the same block with the decoder's residual stream in fp32 (M324_BF16_DECODER=0): what the precision shortcut buys
@@ -738,27 +770,31 @@ def run_infer(args, D: Dist):
             blk_replay = {"error": f"{type(e).__name__}: {e}"[:300]}
     # per-kernel HIP-event timing (roofline object): the same K steps again, launched eagerly on the same
     # stream with an event pair around every GEMM / attention launch (events cannot sit inside a graph)
-    rec = Recorder()
-    with rec:
-        for _ in range(args.steps):
-            step(eager=True)
-    D.fence()
+    rec = None
+    if args.full:
+        rec = Recorder()
+        with rec:
+            for _ in range(args.steps):
+                step(eager=True)
+        D.fence()
 
     line = None
     if rank == 0:
         frames_per_step = world * w["B"] * w["T"]
         ms = dt / args.steps * 1e3
         value = frames_per_step * args.steps / dt
-        summ = rec.summary()
-        stages = {k: summ.pop(k) for k in list(summ) if k.startswith("stage:")}
-        rows = [r for r in roofline_rows(rec, args.steps) if not r["symbol"].startswith("stage:")]
-        dom = rows[0]                                  # dominant SYMBOL (kernel template + grid) by time per step
-        peak = PEAK_BF16_TFLOPS if args.precision == "bf16" else PEAK_F32_TFLOPS
-        traffic, traffic_src = committed_traffic(dom["symbol"])
-        roof = dict(dominant(dom, peak), traffic=traffic, traffic_source=traffic_src,
-                    timing="HIP events around every launch of an eager pass on the launch stream; the same symbols are in "
-                           f"profiles/{PROFILE_ROUND}_*_kernel_stats.md (rocprofv3 --kernel-trace --stats of this command)",
-                    by_symbol=rows[:18], class_totals=class_totals(summ, args.steps, peak))
+        stages, roof = {}, None
+        if rec is not None:
+            summ = rec.summary()
+            stages = {k: summ.pop(k) for k in list(summ) if k.startswith("stage:")}
+            rows = [r for r in roofline_rows(rec, args.steps) if not r["symbol"].startswith("stage:")]
+            dom = rows[0]                              # dominant SYMBOL (kernel template + grid) by time per step
+            peak = PEAK_BF16_TFLOPS if args.precision == "bf16" else PEAK_F32_TFLOPS
+            traffic, traffic_src = committed_traffic(dom["symbol"])
+            roof = dict(dominant(dom, peak), traffic=traffic, traffic_source=traffic_src,
+                        timing="HIP events around every launch of an eager pass on the launch stream; the same symbols are in "
+                               f"profiles/{PROFILE_ROUND}_*_kernel_stats.md (rocprofv3 --kernel-trace --stats of this command)",
+                        by_symbol=rows[:18], class_totals=class_totals(summ, args.steps, peak))
         flops = algorithmic_flops(w["B"], w["T"], w["N"], w["S"])
         line = {
             "metric": "frames/sec (32-frame clip, 2048 pts, 512x512)", "value": round(value, 2), "unit": "frames/s",
@@ -804,14 +840,14 @@ def run_infer(args, D: Dist):
                                        "(secondary.headline_without_precision_shortcuts has both off)")
         line["switches_non_default"] = switches.non_default()
         ref = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb, ref = cpu_baseline(sd, sample_np, w["frames"])
             line["cpu_baseline"] = cb
             err = float((out.double().cpu() - ref.double()).norm() / ref.double().norm())
             line["rel_err_vs_cpu_oracle"] = round(err, 6)
         else:
             line["cpu_baseline"] = None
-        if world == 1 and fast is not None and not args.no_secondary:
+        if args.full and world == 1 and fast is not None and not args.no_secondary:
             line["secondary"] = secondary_measurements(args, D, model, sd, sample, sample_np, ref, headline_ms=ms)
     return line
 
@@ -843,11 +879,17 @@ def run_train(args, D: Dist):
     for _ in range(args.warmup):
         step()
     dt, _ = timed(D, step, args.steps)
-    from motion324_amd.timing import Recorder
-    rec = Recorder()
-    with rec:                                     # one more step with an event pair around every GEMM / attention-forward launch
-        step()
-    D.fence()
+    if args.dump_outputs and rank == 0:           # the last step's loss and gradient norm, the updated weights and the gradients
+        dump_outputs(args.dump_outputs, {"loss": torch.as_tensor(losses[-1]),
+                                         "grad_norm": torch.tensor(infos[-1]["grad_norm"], dtype=torch.float64),
+                                         "params": opt.flat_param, "grads": opt.flat_grad})
+    rec = None
+    if args.full:
+        from motion324_amd.timing import Recorder
+        rec = Recorder()
+        with rec:                                 # one more step with an event pair around every GEMM / attention-forward launch
+            step()
+        D.fence()
     line = None
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -867,9 +909,10 @@ def run_train(args, D: Dist):
                 "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
                 "activations": ("block internals kept in HBM while they fit half of the free memory (M324_TRAIN_STORE=1)"
                                 if training.TRAIN_STORE != "0" else "checkpoint per block + recompute (M324_TRAIN_STORE=0)"),
-                "roofline": roofline_from(rec, 1, args.precision, "HIP events around every GEMM / attention-forward launch of one extra "
-                                          "training step (forward, dgrad, wgrad; the attention backward kernels are "
-                                          f"not in the classes); symbols as in profiles/{PROFILE_ROUND}_train_p1_kernel_stats.md"),
+                "roofline": None if rec is None else roofline_from(
+                    rec, 1, args.precision, "HIP events around every GEMM / attention-forward launch of one extra training step "
+                    "(forward, dgrad, wgrad; the attention backward kernels are not in the classes); symbols as in "
+                    f"profiles/{PROFILE_ROUND}_train_p1_kernel_stats.md"),
                 "cpu_baseline": None}
     return line
 
@@ -916,14 +959,18 @@ def run_frame_parallel(args, D: Dist):
     for _ in range(args.warmup):
         step()
     dt, _ = timed(D, step, args.steps)
-    from motion324_amd.timing import Recorder
-    rec = Recorder()
-    with rec, torch.no_grad():                    # one eager forward with an event pair around every GEMM / attention launch
-        if collect:
-            fp(sample)
-        else:
-            model(sample)
-    D.fence()
+    if args.dump_outputs and rank == 0:           # the whole clip's offsets (the frame-parallel forward gathers them on every rank)
+        dump_outputs(args.dump_outputs, {"pcd_moved": last[0]})
+    rec = None
+    if args.full:
+        from motion324_amd.timing import Recorder
+        rec = Recorder()
+        with rec, torch.no_grad():                # one eager forward with an event pair around every GEMM / attention launch
+            if collect:
+                fp(sample)
+            else:
+                model(sample)
+        D.fence()
     line = None
     if rank == 0:
         flops = algorithmic_flops(1, T, 2048, args.surface)
@@ -941,8 +988,9 @@ def run_frame_parallel(args, D: Dist):
                 "end_to_end_tflops": round(flops * args.steps / dt / 1e12, 1),
                 "end_to_end_frac_of_bf16_peak": round(flops * args.steps / dt / 1e12 / PEAK_BF16_TFLOPS / world, 4),
                 "finite": bool(torch.isfinite(last[0]).all()), "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
-                "roofline": roofline_from(rec, 1, args.precision, "HIP events around every GEMM / attention launch of one eager forward "
-                                          "on the launch stream (rank 0)"),
+                "roofline": None if rec is None else roofline_from(
+                    rec, 1, args.precision, "HIP events around every GEMM / attention launch of one eager forward on the launch "
+                    "stream (rank 0)"),
                 "cpu_baseline": None}
     return line
 
@@ -957,12 +1005,19 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="train mode: batch_size_per_gpu (c3: 8, c4: 32)")
     ap.add_argument("--frames", type=int, default=256, help="frame-parallel mode: clip length (training.frames)")
     ap.add_argument("--surface", type=int, default=4096, help="frame-parallel mode: surface samples (the shell script uses 16384)")
-    ap.add_argument("--sustain", type=float, default=3.0, help="infer mode: seconds of back-to-back replays for the `sustained` field (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-two-in-flight", action="store_true", help="infer mode: skip the extra two-clips-in-flight measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything past the headline as well (a few minutes): `roofline` (an instrumented eager pass), "
+                         "`cpu_baseline` and the oracle comparison, `sustained`, two clips in flight, the decoder-block replay, "
+                         "`secondary`; a plain run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy")
+    ap.add_argument("--sustain", type=float, default=3.0,
+                    help="infer mode with --full: seconds of back-to-back replays for the `sustained` field (0 = off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle")
+    ap.add_argument("--no-two-in-flight", action="store_true", help="infer mode with --full: skip the two-clips-in-flight measurement")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="infer mode: skip the `secondary` object (c3 training step, 256-frame clip, fp32 parity mode, headline "
-                         "without the precision shortcuts, H2D copy)")
+                    help="infer mode with --full: skip the `secondary` object (c3 training step, 256-frame clip, fp32 parity mode, "
+                         "headline without the precision shortcuts, H2D copy)")
     ap.add_argument("--eager", action="store_true", help="time eager per-kernel launches instead of hipGraph replay")
     ap.add_argument("--dino-streams", type=int, default=2, choices=[1, 2],
                     help="image encoder inside the hipGraph: 2 = two half-batches of frames as two branches (default), 1 = one chain (A/B)")

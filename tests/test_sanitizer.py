@@ -86,8 +86,12 @@ def test_host_side_of_the_c_abi_is_clean_under_asan_and_ubsan():
     lib = build.build_sanitized()
     rt = build.sanitizer_runtime()
     assert os.path.exists(lib) and os.path.exists(rt), (lib, rt)
-    env = dict(os.environ, M324_LIB=lib, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    # The child sees no GPU, as on a machine without one: where a device is visible, the HIP runtime allocates device memory
+    # while it starts, and the ASan runtime's allocation interceptors take those calls over (and fail).  The ASan runtime goes
+    # first in LD_PRELOAD, ahead of anything the environment already preloads.
+    preload = ":".join([rt] + [p for p in os.environ.get("LD_PRELOAD", "").replace(" ", ":").split(":") if p])
+    env = dict(os.environ, M324_LIB=lib, LD_PRELOAD=preload, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1",
+               ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([sys.executable, "-c", DRIVER, REPO], capture_output=True, text=True, env=env, timeout=600)
     out = r.stdout + r.stderr
     assert r.returncode == 0 and "SAN_OK" in r.stdout, out[-4000:]

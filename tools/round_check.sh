@@ -5,7 +5,7 @@
 out=gpurun_out/${1:-round_check}; mkdir -p $out
 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.txt 2>&1; tail -3 $out/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; tail -2 $out/smoke.txt
-python bench.py > $out/bench.json 2> $out/bench.err; tail -c 600 $out/bench.json
+python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 600 $out/bench.json
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout 600 rocprofv3 --kernel-trace --stats -d $out/trace -o kt -- python3 tools/train_bench.py --batch 8 --steps 3 --warmup 2 > $out/train_profiled.json 2> $out/trace.err
 db=$(find $out/trace -name "*.db" | head -1)
