@@ -14,7 +14,8 @@
  *   - return 0 on success, negative m324_status on failure; m324_last_error() gives the text of
  *     the calling thread's last failure.  Nothing throws or aborts across the boundary.
  *   - dtype codes: M324_F32 = fp32 "parity" arithmetic (f32 MFMA, exact), M324_BF16 = bf16 operands
- *     with fp32 accumulation ("speed" mode, what the reference runs under torch.autocast(bf16)).
+ *     with fp32 accumulation ("speed" mode, what the reference runs under torch.autocast(bf16)), M324_MXFP8 = block-scaled
+ *     e4m3 operands (m324_gemm_mx only; the opt-in "mxfp8" inference precision).
  *   - matrices are row-major; `ld*` are leading dimensions in ELEMENTS.
  */
 #ifndef M324_H
@@ -25,7 +26,7 @@ extern "C" {
 #endif
 
 typedef enum { M324_OK = 0, M324_ERR_INVALID = -1, M324_ERR_HIP = -2, M324_ERR_UNSUPPORTED = -3 } m324_status;
-typedef enum { M324_F32 = 0, M324_BF16 = 1 } m324_dtype;
+typedef enum { M324_F32 = 0, M324_BF16 = 1, M324_MXFP8 = 2 } m324_dtype;
 typedef enum { M324_ACT_NONE = 0, M324_ACT_GELU = 1 } m324_act;
 /* aux_mode of m324_gemm (aux has the output dtype and layout [M, ldaux], no row remap):
  *   M324_AUX_STORE_PREACT  : aux[m,n] = acc + bias, the value the activation is applied to -- one launch gives the
@@ -126,6 +127,30 @@ int m324_gemm_pair(const m324_gemm_args* a, const m324_gemm_args* b, void* strea
  * launch for `a` into buf; returns the schedule number.  bench.py labels its per-launch HIP-event rows with it so that
  * they can be matched against the committed rocprofv3 summaries (profiles/). */
 int m324_gemm_plan(const m324_gemm_args* a, char* buf, int n);
+
+/* ------------------------------------------------------------------------------------------
+ * MX (block-scaled FP8) operands -- the opt-in "mxfp8" inference precision of the trunk and DINOv2 q|k|v / fc1 / fc2 GEMMs.
+ *   An MX matrix [rows, K] is q [rows, ldq] OCP e4m3fn bytes + s [rows, lds] E8M0 scale bytes (value 2^(s - 127)), one
+ *   scale per 32 consecutive K of a row.  Rule, per block of 32 values: X = ceil(log2(amax / 448)) clamped to [-127, 127],
+ *   s = X + 127, q = v * 2^-X rounded to nearest even e4m3 (never saturates); an all-zero block has s = 0 and zero elements,
+ *   a block holding NaN / Inf has s = 0xFF (NaN) and NaN elements (0x7F).
+ * m324_mx_quant: x [rows, K] (x_dtype fp32 / bf16, K % 32 == 0, 16-byte rows) -> q, s.  Weights, once per weight version.
+ * m324_layernorm_mx: the fp32 residual stream -> LayerNorm (w, optional b, eps; m324_layernorm's arithmetic) -> q, s in one
+ *   pass (C % 32 == 0, C <= 1024).  Replaces the LayerNorm in front of the MX projections (transformer.py:400,411; DINOv2
+ *   norm1 / norm2).
+ * m324_gemm_mx: C = epilogue(A . W^T) with A = a->A / A_scale [M, lds_a], W = a->W / W_scale [N, lds_w] MX operands
+ *   (a->in_dtype = M324_MXFP8, lda / ldw in bytes), v_mfma_scale_f32_32x32x64_f8f6f4, fp32 accumulation.
+ *   K % 128 == 0, N % 64 == 0, operand rows 16-byte aligned, scale rows 4-byte aligned, batch <= 1.  Built epilogues:
+ *     out_dtype bf16: + bias, either stored at C or the q|k|v heads (M324_AUX_QKV_HEADS / _VT, as m324_gemm);
+ *     out_dtype fp32: + bias, * gamma, + residual where residual == C (the residual stream updated in place);
+ *     out_dtype M324_MXFP8: + bias, GELU (act), quantised by the rule above into C [M, ldc] + C_scale [M, lds_c] (fc1 -> fc2).
+ *   Anything else (row map, LayerNorm fold, aux modes, ...) returns M324_ERR_UNSUPPORTED without launching.
+ * ------------------------------------------------------------------------------------------ */
+int m324_mx_quant(const void* x, int x_dtype, long ldx, int rows, int K, void* q, long ldq, void* s, long lds, void* stream);
+int m324_layernorm_mx(const float* x, long ldx, const float* w, const float* b, float eps, int rows, int C, void* q, long ldq,
+                      void* s, long lds, void* stream);
+int m324_gemm_mx(const m324_gemm_args* a, const void* A_scale, long lds_a, const void* W_scale, long lds_w, void* C_scale,
+                 long lds_c, void* stream);
 
 /* LayerNorm fold, between producer and consumer: rowstat[m] = (rstd, -rstd mean) of row m from the ncb per-block
  * (sum, M2) pairs part[cb][m] a producer GEMM left (blocks of 64 columns, C = 64 ncb);  eps as in nn.LayerNorm. */

@@ -30,7 +30,9 @@ from .lib import ACT_GELU, M324Error
 from .loss import MSELossComputer
 from .prepared import Prepared, bump_generation, compute_dtype, pad_k
 from .timing import span
-from .transformer import LN_EPS, LNFold, QK_Norm_CrossAttentionBlock, QK_Norm_TransformerBlock, init_weights
+from . import transformer as _transformer
+from .transformer import (LN_EPS, LNFold, QK_Norm_CrossAttentionBlock, QK_Norm_TransformerBlock, fusion_off, init_weights,
+                          mx_scope)
 
 # A/B switches: one table with defaults and meanings in motion324_amd/switches.py (bench.py echoes non-default values)
 AUTO_GRAPH = switches.flag("M324_AUTO_GRAPH")               # forward(): graph replay for repeated inference shapes
@@ -40,6 +42,7 @@ KV_OVERLAP = switches.flag("M324_KV_OVERLAP")              # frame-parallel: own
 BF16_DECODER_STREAM = switches.flag("M324_BF16_DECODER")    # the decoder's residual stream in bf16 (bf16 inference only)
 HOIST_DECODER_Q = switches.flag("M324_HOIST_Q")             # hoisted decoder q projection (graph capture)
 DECODE_ROWS = int(switches.get("M324_DECODE_ROWS"))         # max (frames x points) rows per decoder pass: bounds the [rows, 4C] MLP buffer
+MXFP8_DEFAULT = switches.flag("M324_MXFP8")                # inference_precision of a model whose config names none: "mxfp8" (1) / "bf16"
 
 
 def _get(cfg, key, default=None):
@@ -320,6 +323,30 @@ class Motion_Latent_Model(nn.Module):
         self.loss_computer = MSELossComputer(self.config)
         self.auto_graph = AUTO_GRAPH            # inference: repeated shapes are served by hipGraph replay (forward())
         self.auto_graph_after = 2
+        # inference precision of a bf16 forward: "bf16", or "mxfp8" (opt-in: the GEMM roles of
+        # transformer.MX_ROLES -- the trunk and DINOv2 q|k|v projections -- on block-scaled e4m3 operands); config
+        # model.inference_precision, else the M324_MXFP8 switch
+        ip = _get(model_cfg, "inference_precision", None)
+        self.inference_precision = ip if ip is not None else ("mxfp8" if MXFP8_DEFAULT else "bf16")
+
+    @property
+    def inference_precision(self) -> str:
+        return self.__dict__["_inference_precision"]
+
+    @inference_precision.setter
+    def inference_precision(self, value: str) -> None:
+        if value not in ("bf16", "mxfp8"):
+            raise ValueError(f"inference_precision must be 'bf16' or 'mxfp8', got {value!r}")
+        if value == "mxfp8" and self.embed_dim % 128 != 0:
+            raise NotImplementedError(f"inference_precision 'mxfp8' needs transformer.d % 128 == 0 (m324_gemm_mx: K % 128 == 0), "
+                                      f"got d = {self.embed_dim}")
+        self.__dict__["_inference_precision"] = value
+
+    def mx_effective(self) -> bool:
+        """Does a forward called now run the MXFP8 mode?  Only a bf16 inference forward: setting "mxfp8", bf16 compute dtype,
+        eval mode, grad off and not inside a training step (transformer.fusion_disabled)."""
+        return (self.inference_precision == "mxfp8" and compute_dtype() == torch.bfloat16 and not self.training
+                and not torch.is_grad_enabled() and not fusion_off())
 
     def train(self, mode=True):
         # the reference's override returns None (Pcd_motion.py:372-373); returning self keeps
@@ -400,7 +427,7 @@ class Motion_Latent_Model(nn.Module):
                 or torch.cuda.is_current_stream_capturing():
             return None
         from .graph import GraphedForward, shape_key
-        key = (compute_dtype(),) + shape_key(sample)
+        key = (compute_dtype(), self.mx_effective()) + shape_key(sample)
         seen = self.__dict__.setdefault("_ag_seen", {})
         if key not in seen and len(seen) >= 8:               # a caller that keeps changing shapes: forget the oldest
             del seen[next(iter(seen))]
@@ -488,6 +515,8 @@ class Motion_Latent_Model(nn.Module):
         (a loader that decodes its shard: at T = 256 the full fp32 clip is 805 MB of host-to-device traffic per rank, 7/8 of
         it for frames the rank never touches); total_frames = the clip's length."""
         from . import parallel
+        if self.inference_precision == "mxfp8":
+            raise M324Error("forward_frame_parallel: inference_precision 'mxfp8' is single-GPU only (set model.inference_precision = 'bf16')")
         rank, world = parallel.world_info(group)
         if local_frames and (total_frames is None or total_frames < 1):
             raise M324Error("forward_frame_parallel(local_frames=True) needs total_frames")
@@ -500,6 +529,7 @@ class Motion_Latent_Model(nn.Module):
             raise M324Error("motion324_amd.Motion_Latent_Model runs only on a HIP device (model.to('cuda'), inputs on "
                             "'cuda'); there is no CPU fallback on this path")
         P = Prepared.for_module(self, dev, compute_dtype())
+        mx = mx_scope(_transformer.MX_ROLES if shard is None and self.mx_effective() else ())      # MXFP8: image encoder + trunk
         cap = getattr(self, "_capture", None)      # tests: dict that receives clones of stage activations
         B, N, _ = ref_pcd.shape
         C, K = self.embed_dim, self.num_learnable_tokens
@@ -573,11 +603,13 @@ class Motion_Latent_Model(nn.Module):
                 raise M324Error(f"m324_anchor_tokens: expected [{1 + Pn}, {C}] with one sample per call, got {tuple(anchor_in.shape)} (B = {B})")
             dino_x = torch.empty(((T + 1) * (1 + Pn), C), dtype=torch.float32, device=dev)
             ops.cast(self._f32c(anchor_in), torch.float32, out=dino_x[:1 + Pn])      # m324_cast fp32 -> fp32: a row copy
-            self.image_encoder.run(P, video.reshape(T, Hin, Win, 3), out=dino_x[1 + Pn:])
+            with mx:
+                self.image_encoder.run(P, video.reshape(T, Hin, Win, 3), out=dino_x[1 + Pn:])
             T += 1
             T_full = T
         else:
-            dino_x = self.image_encoder.run(P, video.reshape(B * T, Hin, Win, 3))
+            with mx:
+                dino_x = self.image_encoder.run(P, video.reshape(B * T, Hin, Win, 3))
 
         if side is not None:                      # join: the assembly reads the latent tokens
             main_stream.wait_stream(side)
@@ -607,12 +639,15 @@ class Motion_Latent_Model(nn.Module):
 
         # LayerNorm fold (transformer.LNFold): the statistics of the stream travel from GEMM epilogue to GEMM epilogue
         fold = None
-        if LNFold.usable(P, tok.shape[0], C):
-            fold = LNFold(tok).from_stream(tok, self.global_transformer_blocks[0].norm1.eps)
+        if LNFold.usable(P, tok.shape[0], C) and "trunk.mlp" not in mx.roles:       # (MXFP8 MLP: no fold, transformer.MX_ROLES)
+            fold = LNFold(tok)
+            if "trunk.qkv" not in mx.roles:            # an MX q|k|v projection normalises the stream itself
+                fold.from_stream(tok, self.global_transformer_blocks[0].norm1.eps)
         n_pairs = len(self.global_transformer_blocks)
         for i, (gblk, lblk) in enumerate(zip(self.global_transformer_blocks, self.local_transformer_blocks)):
-            gblk.run(P, tok, B, T * Lt, kv_gather=kv_gather, fold=fold)
-            lblk.run(P, tok, B * T, Lt, fold=fold, feed_next=i + 1 < n_pairs)     # the decoder gathers its own rows
+            with mx:
+                gblk.run(P, tok, B, T * Lt, kv_gather=kv_gather, fold=fold)
+                lblk.run(P, tok, B * T, Lt, fold=fold, feed_next=i + 1 < n_pairs)     # the decoder gathers its own rows
             if cap is not None and "trunk_block0" not in cap:
                 cap["trunk_block0"] = tok.clone()
         if cap is not None:

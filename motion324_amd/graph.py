@@ -124,7 +124,12 @@ class GraphedForward:
         self._graphs.clear()
 
     def _key(self, sample) -> Tuple:
-        return (prepared.generation(), prepared.weight_stamp(self.model), compute_dtype()) + shape_key(sample)
+        # the effective inference precision mode too, as the captured forward sees it (eval mode, grad off): a graph captured in
+        # one mode is never replayed for the other
+        mx = getattr(self.model, "mx_effective", None)
+        with torch.no_grad():
+            mx = bool(mx()) if mx is not None else False
+        return (prepared.generation(), prepared.weight_stamp(self.model), compute_dtype(), mx) + shape_key(sample)
 
     def static_inputs(self, sample: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """The graph's own input buffers for this sample's shapes (captured on first use), holding a copy of `sample`.

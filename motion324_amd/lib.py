@@ -12,9 +12,9 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("M324_LIB") or os.path.join(HERE, "libm324.so")      # M324_LIB: lab builds (tools/lablibs)
 
-F32, BF16 = 0, 1
+F32, BF16, MXFP8 = 0, 1, 2
 ACT_NONE, ACT_GELU = 0, 1
-ABI_VERSION = 22
+ABI_VERSION = 23
 ERR_UNSUPPORTED = -3          # m324_status M324_ERR_UNSUPPORTED
 
 
@@ -67,6 +67,9 @@ SIGNATURES = {
     "m324_gemm": [C.POINTER(GemmArgs), _P],
     "m324_gemm_plan": [C.POINTER(GemmArgs), C.c_char_p, _I],
     "m324_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _P],
+    "m324_mx_quant": [_P, _I, _L, _I, _I, _P, _L, _P, _L, _P],
+    "m324_layernorm_mx": [_P, _L, _P, _P, _F, _I, _I, _P, _L, _P, _L, _P],
+    "m324_gemm_mx": [C.POINTER(GemmArgs), _P, _L, _P, _L, _P, _L, _P],
     "m324_attention_plan": [_I, _I, _I, _I, _I, _I, C.c_char_p, _I],
     "m324_gemm_tn": [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _L, _P],
     "m324_n3_finish": [_P, _I, _I, _P, _P, _P],

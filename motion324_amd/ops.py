@@ -7,7 +7,7 @@ live on a HIP device -- there is deliberately no CPU / eager fallback.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -15,7 +15,7 @@ from . import lib as L
 from . import switches
 from .timing import active as _timing, span
 
-F32, BF16 = L.F32, L.BF16
+F32, BF16, MXFP8 = L.F32, L.BF16, L.MXFP8
 _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16}
 
 
@@ -300,6 +300,111 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
     with span(f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * K, nbytes, tag):
         L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
     return out
+
+
+class MX(NamedTuple):
+    """A block-scaled FP8 operand (include/m324.h, "MX operands"): q uint8 [rows, >= K] OCP e4m3fn element bytes and s uint8
+    [rows, >= K / 32] E8M0 scale bytes, one per 32 consecutive K of a row."""
+    q: torch.Tensor
+    s: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+
+def mx_empty(rows: int, K: int, device) -> MX:
+    """Storage for an MX matrix [rows, K]; scale rows padded to 4 bytes (m324_gemm_mx reads one dword per row and K-tile)."""
+    return MX(torch.empty((rows, K), dtype=torch.uint8, device=device),
+              torch.empty((rows, (K // 32 + 3) // 4 * 4), dtype=torch.uint8, device=device)[:, :K // 32])
+
+
+def _mx_rows(t: MX, rows: int, K: int, name: str):
+    if (not isinstance(t, MX) or t.q.dtype != torch.uint8 or t.s.dtype != torch.uint8 or t.q.shape[0] < rows or t.q.shape[1] < K
+            or t.s.shape[0] < rows or t.s.shape[1] < K // 32):
+        raise L.M324Error(f"{name}: expected an MX operand of at least [{rows}, {K}]")
+    (pq, lq), (ps, ls) = _rows(t.q, name + ".q"), _rows(t.s, name + ".s")
+    return pq, lq, ps, ls
+
+
+def mx_quant(x: torch.Tensor, out: Optional[MX] = None) -> MX:
+    """x fp32 / bf16 [rows, K] (K % 32 == 0) -> MX operand by the rule of include/m324.h (m324_mx_quant)."""
+    rows, K = x.shape
+    out = mx_empty(rows, K, x.device) if out is None else out
+    px, ldx = _rows(x, "x")
+    pq, lq, ps, ls = _mx_rows(out, rows, K, "out")
+    with span("hbm_pass", 0.0, float(rows) * K * (x.element_size() + 1), f"mx_quant_kernel | rows={rows} K={K}" if _timing() else ""):
+        L.check(L.load().m324_mx_quant(px, code_of(x.dtype), ldx, rows, K, pq, lq, ps, ls, _stream()), "m324_mx_quant")
+    _wrote(out.q, out.s)
+    return out
+
+
+def layernorm_mx(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float, out: Optional[MX] = None) -> MX:
+    """LayerNorm of the fp32 stream x [rows, C] straight into an MX operand (m324_layernorm_mx)."""
+    if x.dtype != torch.float32:
+        raise L.M324Error("layernorm_mx: x must be fp32")
+    rows, Cdim = x.shape
+    out = mx_empty(rows, Cdim, x.device) if out is None else out
+    px, ldx = _rows(x, "x")
+    pq, lq, ps, ls = _mx_rows(out, rows, Cdim, "out")
+    with span("hbm_pass", 0.0, float(rows) * Cdim * 5, f"layernorm_mx_kernel | rows={rows} C={Cdim}" if _timing() else ""):
+        L.check(L.load().m324_layernorm_mx(px, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, rows, Cdim, pq, lq, ps, ls, _stream()),
+                "m324_layernorm_mx")
+    _wrote(out.q, out.s)
+    return out
+
+
+def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, residual: Optional[torch.Tensor] = None,
+            qkv_heads: Optional[tuple] = None):
+    """out = epilogue(a @ w^T) on MX operands (m324_gemm_mx).  Epilogues: `out` bf16 [M, N] (+ bias); qkv_heads as in gemm()
+    (`out` None); `out` the fp32 residual stream with residual=out (+ bias, * gamma); `out` an MX operand [M, N] (+ bias, GELU
+    with act=ACT_GELU).  Returns `out` (the first head-major output for qkv_heads)."""
+    M, K = a.q.shape[0], a.q.shape[1]
+    N = w.q.shape[0]
+    pa, la, psa, lsa = _mx_rows(a, M, K, "a")
+    pw, lw, psw, lsw = _mx_rows(w, N, K, "w")
+    args = L.GemmArgs()
+    args.A, args.lda, args.W, args.ldw = pa, la, pw, lw
+    args.M, args.N, args.K = M, N, K
+    args.in_dtype, args.batch = MXFP8, 1
+    args.bias = _vec(bias, N, "bias")
+    args.act = act
+    args.gamma = _vec(gamma, N, "gamma")
+    pcs, lcs = None, 0
+    first = out
+    if qkv_heads is not None:
+        Qo, Ko, Vo, qw, kw, eps, q_scale, Lh, Hh = qkv_heads[:9]
+        Bh = M // Lh
+        vt = Vo is not None and tuple(Vo.shape) == (Bh, Hh, 64, Lh) and Lh != 64
+        for t in (Qo, Ko, Vo):
+            if t is None:
+                continue
+            want = (Bh, Hh, 64, Lh) if (vt and t is Vo) else (Bh, Hh, Lh, 64)
+            if t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != want:
+                raise L.M324Error(f"gemm_mx: qkv_heads output {t.dtype}{tuple(t.shape)} (want bf16 {want})")
+        args.C, args.ldc, args.out_dtype = None, N, BF16
+        args.aux_mode = 4 if vt else 3
+        args.qkv_q, args.qkv_k, args.qkv_v = _p(Qo), _p(Ko), _p(Vo)
+        args.qkv_qw, args.qkv_kw = _vec(qw, 64, "q_w"), _vec(kw, 64, "k_w")
+        args.qkv_eps, args.qkv_qscale, args.qkv_L, args.qkv_H = eps, q_scale, Lh, Hh
+        first = next(t for t in (Qo, Ko, Vo) if t is not None)
+        _wrote(Qo, Ko, Vo)
+    elif isinstance(out, MX):
+        args.C, args.ldc, pcs, lcs = _mx_rows(out, M, N, "out")
+        args.out_dtype = MXFP8
+        _wrote(out.q, out.s)
+    else:
+        args.C, args.ldc = _rows(out, "out")
+        args.out_dtype = code_of(out.dtype)
+        if out.shape[0] < M or out.shape[1] < N:
+            raise L.M324Error(f"gemm_mx: out{tuple(out.shape)} too small for {M} x {N}")
+        if residual is not None:
+            args.residual, args.ldr = _rows(residual, "residual")
+        _wrote(out)
+    with span("gemm_mx", 2.0 * M * N * K, float(M * K + N * K + M * N * 2),
+              f"gemm_mx_kernel | M={M} N={N} K={K}" if _timing() else ""):
+        L.check(L.load().m324_gemm_mx(C.byref(args), psa, lsa, psw, lsw, pcs, lcs, _stream()), "m324_gemm_mx")
+    return first
 
 
 def gemm_pair(deferred: list) -> None:

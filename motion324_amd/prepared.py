@@ -178,6 +178,16 @@ class Prepared:
             return es[0].base[es[0].off:es[-1].off + es[-1].mat.numel()].view(-1, k)
         return self._get("cat", tuple(ps), lambda: torch.cat([self._mat_of(p) for p in ps], dim=0).contiguous())
 
+    def mx(self, p: torch.Tensor):
+        """MX operand (ops.MX: e4m3 elements + E8M0 scales, m324_mx_quant of the fp32 weight) of a Linear weight [N, K], K % 32 == 0
+        -- the MXFP8 inference mode's operand; derived once per weight version like mat()."""
+        from . import ops
+
+        def make():
+            w = p.detach().reshape(p.shape[0], -1).to(device=self.device, dtype=torch.float32).contiguous()
+            return ops.mx_quant(w)
+        return self._get("mx", (p,), make)
+
     def vec(self, p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """fp32 epilogue / normalisation vector (bias, LN weight, LayerScale gamma ...)."""
         if p is None:

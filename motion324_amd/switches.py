@@ -34,6 +34,7 @@ HOST: Dict[str, Tuple[str, str, str]] = {
     "M324_GELU_GRAD_FWD": ("1", "backward.GELU_GRAD_FWD", "training: the fc1 GEMM of every MLP leaves gelu'(z) next to gelu(z) (M324_AUX_STORE_GELU_GRAD) and the dgrad GEMM behind fc2 multiplies by it (M324_AUX_MUL); 0: it leaves z and the dgrad epilogue evaluates erf and exp again"),
     "M324_WEIGHT_MIRROR": ("1", "optim.WEIGHT_MIRROR", "training: FusedAdamW keeps bf16 row-major and transposed copies of every Linear weight in two flat buffers, rewritten by one m324_weight_mirror launch after each update (0: Prepared casts / m324_transpose per weight and step)"),
     "M324_DEFER_COLSUM": ("1", "ops.DEFER_COLSUM", "training: the sums of the weight gradients' split-K partials and of the norm-weight partials wait in a queue and leave in one m324_colsum_multi launch per block (0: one m324_colsum launch each, at once)"),
+    "M324_MXFP8": ("0", "Pcd_motion.MXFP8_DEFAULT", "1: a model whose config names no model.inference_precision uses \"mxfp8\" -- block-scaled e4m3 operands for the GEMM roles of transformer.MX_ROLES (the trunk and DINOv2 q|k|v projections) in a bf16 inference forward (DESIGN section 4)"),
     "M324_PRECISION": ("", "prepared.compute_dtype()", "force bf16 / fp32 (default: follow torch.autocast like the reference)"),
     "M324_LIB": ("", "lib.LIB_PATH", "path of an alternative libm324.so (lab builds)"),
     "M324_RCCL_LIB": ("", "csrc/comm.hip", "m324_comm_*: path of the RCCL library to bind (default: the copy already loaded, else librccl.so)"),

@@ -192,11 +192,19 @@ def hp_consumer(rows: int, n_out: int, k: int) -> bool:
 
 
 def _mlp_residual(P: Prepared, norm2: nn.LayerNorm, mlp: MLP, x: torch.Tensor, fold: Optional[LNFold] = None,
-                  feed_next: bool = True) -> torch.Tensor:
+                  feed_next: bool = True, mx: bool = False) -> torch.Tensor:
     """x += fc2(gelu(fc1(LN(x))))  (reference transformer.py:376,422), x [rows, C] (fp32, or the decoder's bf16 stream), in
-    place.  fold: the stream's LNFold with statistics pending or ready; fc2 then leaves the next LayerNorm's (feed_next)."""
+    place.  fold: the stream's LNFold with statistics pending or ready; fc2 then leaves the next LayerNorm's (feed_next).
+    mx: the MLP runs on MX operands (the caller asked mx_role(P, ...); the fp32 stream, no fold)."""
     rows, C = x.shape
     fc1, fc2 = mlp.mlp[0], mlp.mlp[2]
+    if mx and fold is None and x.dtype == torch.float32:
+        # MXFP8: LayerNorm straight into an MX operand, fc1 + GELU into another, fc2 updates the fp32 stream
+        a2 = ops.layernorm_mx(x, P.vec(norm2.weight), P.vec(norm2.bias), norm2.eps)
+        hq = ops.mx_empty(rows, fc1.out_features, x.device)
+        ops.gemm_mx(a2, P.mx(fc1.weight), hq, bias=P.vec(fc1.bias), act=ACT_GELU)
+        ops.gemm_mx(hq, P.mx(fc2.weight), x, bias=P.vec(fc2.bias), residual=x)
+        return x
     h1 = torch.empty((rows, fc1.out_features), dtype=P.dtype, device=x.device)
     if fold is not None:
         w1, cs1, b1 = P.folded(norm2.weight, norm2.bias, fc1.weight, fc1.bias)
@@ -222,15 +230,60 @@ _FUSE_OFF = 0
 
 class fusion_disabled:
     """Training steps run their forward inside this context (the backward recomputes with m324_qkv_split's training
-    outputs, and an autograd.Function's forward runs with grad mode off, so grad mode alone cannot tell)."""
+    outputs, and an autograd.Function's forward runs with grad mode off, so grad mode alone cannot tell).  It also closes any
+    MXFP8 scope (mx_scope below): a training step -- its frozen DINO included, which fusion_allowed() reopens -- stays bf16."""
 
     def __enter__(self):
-        global _FUSE_OFF
+        global _FUSE_OFF, _MX_ROLES_ON
         _FUSE_OFF += 1
+        self._mx, _MX_ROLES_ON = _MX_ROLES_ON, frozenset()
 
     def __exit__(self, *exc):
-        global _FUSE_OFF
+        global _FUSE_OFF, _MX_ROLES_ON
         _FUSE_OFF -= 1
+        _MX_ROLES_ON = self._mx
+
+
+def fusion_off() -> bool:
+    """Inside a training step's fusion_disabled()."""
+    return _FUSE_OFF > 0
+
+
+# Opt-in MXFP8 inference (Motion_Latent_Model.inference_precision = "mxfp8", DESIGN section 4): the GEMM roles that run on
+# block-scaled e4m3 operands (include/m324.h, "MX operands").  THE table: tools and profiles switch roles by rebinding MX_ROLES.
+#   "trunk.qkv" / "dino.qkv": LayerNorm -> MX (m324_layernorm_mx), q|k|v projection on MX operands (m324_gemm_mx);
+#   "trunk.mlp" / "dino.mlp": LayerNorm -> MX, fc1 + GELU with an MX output, fc2 on that output (fc1's MX output IS fc2's
+#   operand: the two switch together).
+# Out-projections, attention, the shape encoder, the decoder and the head stay bf16.  A stream whose MLP role is on has no LayerNorm
+# fold (a quantised raw stream would carry e4m3 error times |mean| / std through the fold's epilogue); with only its q|k|v role on,
+# the fold stays for fc1.
+# Measured (profiles/mxfp8.md, one MI355X, interleaved): q|k|v with its LayerNorm -> MX pass 0.90-0.93x of today's folded bf16
+# GEMM; fc1 1.02-1.10x and fc2 1.05x -- the MLP roles do not win with m324_gemm_mx's two-stage 128 x 128 pipeline and stay bf16.
+MX_ROLES_BUILT = frozenset({"trunk.qkv", "trunk.mlp", "dino.qkv", "dino.mlp"})
+MX_ROLES = frozenset({"trunk.qkv", "dino.qkv"})
+_MX_ROLES_ON: frozenset = frozenset()
+
+
+class mx_scope:
+    """The roles (subset of MX_ROLES) the code inside runs on MX operands; Motion_Latent_Model._forward opens it around the image
+    encoder and the trunk when the mode is in effect (inference_precision "mxfp8", bf16, eval, grad off, no training step)."""
+
+    def __init__(self, roles):
+        self.roles = frozenset(roles)
+
+    def __enter__(self):
+        global _MX_ROLES_ON
+        self._saved, _MX_ROLES_ON = _MX_ROLES_ON, self.roles
+        return self
+
+    def __exit__(self, *exc):
+        global _MX_ROLES_ON
+        _MX_ROLES_ON = self._saved
+
+
+def mx_role(P: Prepared, role: str) -> bool:
+    """Does this GEMM role run on MX operands here?  (bf16 inference inside an mx_scope that lists it, never in a training step.)"""
+    return role in _MX_ROLES_ON and not _FUSE_OFF and P.dtype == torch.bfloat16 and not torch.is_grad_enabled()
 
 
 class fusion_allowed:
@@ -286,7 +339,18 @@ class QK_Norm_TransformerBlock(nn.Module):
         a = self.attn
         h = torch.empty((rows, C), dtype=P.dtype, device=x.device)
         qw, kw = a._qk_w(P)
-        if fold is not None:
+        # MXFP8 (mx_scope): the trunk's q|k|v projection / MLP on MX operands, through the unfolded branch shape.  The q|k|v role
+        # reads the fp32 stream itself (m324_layernorm_mx); a stream whose MLP stays bf16 keeps its LayerNorm fold for fc1 (the
+        # out-projection produces the statistics, fc2 produces none: the next block's q|k|v LayerNorm computes its own).
+        mx_qkv = kv_gather is None and mx_role(P, "trunk.qkv")
+        mlp_mx = fold is None and mx_role(P, "trunk.mlp")
+        proj = ops.gemm_mx if mx_qkv else ops.gemm
+        if mx_qkv:
+            src = ops.layernorm_mx(x, P.vec(self.norm1.weight), P.vec(self.norm1.bias), self.norm1.eps)
+            w, bias = P.mx(a.to_qkv.weight), P.vec(a.to_qkv.bias)
+            lnk = lambda lo, hi: {}
+            feed_next = False
+        elif fold is not None:
             w, cs, bias = P.folded(self.norm1.weight, self.norm1.bias, a.to_qkv.weight, a.to_qkv.bias)
             src, lnk = fold.xb, (lambda lo, hi: dict(ln=fold.ln(self.norm1.eps, cs[lo:hi])))
         else:
@@ -300,14 +364,14 @@ class QK_Norm_TransformerBlock(nn.Module):
             long_seq = L >= 2048
             Q, K = (torch.empty((B, a.num_heads, L, 64), dtype=P.dtype, device=x.device) for _ in range(2))
             V = torch.empty((B, a.num_heads, 64, L) if long_seq else (B, a.num_heads, L, 64), dtype=P.dtype, device=x.device)
-            ops.gemm(src, w, None, bias=bias, qkv_heads=(Q, K, V, qw, kw, RMS_EPS, ops.Q_PRESCALE, L, a.num_heads),
-                     **lnk(0, 3 * C))
+            proj(src, w, None, bias=bias, qkv_heads=(Q, K, V, qw, kw, RMS_EPS, ops.Q_PRESCALE, L, a.num_heads),
+                 **lnk(0, 3 * C))
             ops.attention(Q, K, V, h, prescaled=True, v_rowmajor=not long_seq, bounded=long_seq and a.scores_bounded(P))
             ops.gemm(h, P.mat(a.fc.weight), x, bias=P.vec(a.fc.bias), residual=x, **out_kw())
-            return _mlp_residual(P, self.norm2, self.mlp, x, fold, feed_next)
+            return _mlp_residual(P, self.norm2, self.mlp, x, fold, feed_next, mx=mlp_mx)
         if kv_gather is None:
             qkv = torch.empty((rows, 3 * C), dtype=P.dtype, device=x.device)
-            ops.gemm(src, w, qkv, bias=bias, **lnk(0, 3 * C))
+            proj(src, w, qkv, bias=bias, **lnk(0, 3 * C))
             Q, K, Vt = ops.qkv_split(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], qw, kw, RMS_EPS, B, L, a.num_heads,
                                      P.dtype, q_scale=ops.Q_PRESCALE)
         else:
@@ -346,7 +410,7 @@ class QK_Norm_TransformerBlock(nn.Module):
                                      P.dtype)
         ops.attention(Q, K, Vt, h, prescaled=True, bounded=a.scores_bounded(P))          # h reused as the attention output
         ops.gemm(h, P.mat(a.fc.weight), x, bias=P.vec(a.fc.bias), residual=x, **out_kw())
-        return _mlp_residual(P, self.norm2, self.mlp, x, fold, feed_next)
+        return _mlp_residual(P, self.norm2, self.mlp, x, fold, feed_next, mx=mlp_mx)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Stand-alone use: x [B, L, C] on a HIP device; precision follows torch.autocast like the reference."""
