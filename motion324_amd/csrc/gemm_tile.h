@@ -190,7 +190,9 @@ __device__ __forceinline__ void apply_gelu8_grad(float4& v, float4& w, float4& d
     }
 }
 
-// d gelu(z) / dz = Phi(z) + z phi(z).  fp32 outputs: erff / expf; bf16 outputs: the polynomial erf above and exp2.
+// d gelu(z) / dz = Phi(z) + z phi(z).  fp32 outputs: erff / expf; bf16 outputs: a polynomial erf and exp2 -- erf(t) ~ t p(t^2) with the
+// argument t = z / sqrt 2 clamped to +-3 (erf(3) = 0.99998 stands in for 1 beyond): |erf error| <= 1.7e-5 on [-3, 3] (the coefficients
+// below evaluated in fp64 against erf: 1.67e-5, at |t| = 2.956).
 template <typename TOUT>
 __device__ __forceinline__ float gelu_grad(float z) {
     if constexpr (sizeof(TOUT) == 2) {

@@ -4,6 +4,7 @@ import math
 import pytest
 import torch
 
+import error_bounds as eb
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -189,6 +190,9 @@ def test_gelu_forward_backward(dtype):
     tol = 1e-6 if dtype == torch.float32 else 5e-3
     assert rel_err(ops.gelu(z.to(dtype).to(DEV)).float(), h.detach()) < tol
     assert rel_err(ops.gelu_bwd(z.to(dtype).to(DEV), dh.to(dtype).to(DEV)).float(), zt.grad) < tol
+    if dtype == torch.bfloat16:
+        eb.assert_within(ops.gelu(z.to(dtype).to(DEV)), h.detach(), eb.gelu_elementwise(z), "gelu")
+        eb.assert_within(ops.gelu_bwd(z.to(dtype).to(DEV), dh.to(dtype).to(DEV)), zt.grad, eb.gelu_backward(z, dh), "gelu backward")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -277,6 +281,14 @@ def test_attention_backward_against_autograd(dtype, B, H, Lq, Lk, shared):
         got_dq = got_dq.sum(0, keepdim=True)
     assert rel_err(got_dq, dq_ref) < gtol
     assert rel_err(dK.float(), kd.grad) < gtol and rel_err(dV.float(), vd.grad) < gtol
+    if dtype == torch.bfloat16:
+        bound, lse_bound = eb.attention_and_lse(qs, k, v, math.log(2.0))
+        eb.assert_within(out, o.detach(), bound, "forward")
+        eb.assert_within(lse, ref_lse, lse_bound, "lse")
+        bq, bk, bv = eb.attention_backward(qh.detach(), k, v, dO_hm, 64 ** -0.5, p_bf16=False, shared=shared)   # fp32 arithmetic, bf16 O and outputs
+        eb.assert_within(got_dq, dq_ref, bq, "dQ")
+        eb.assert_within(dK, kd.grad, bk, "dK")
+        eb.assert_within(dV, vd.grad, bv, "dV")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -309,6 +321,16 @@ def test_qkv_split_train_outputs_and_backward(dtype):
     tol = 1e-5 if dtype == torch.float32 else 8e-3
     assert rel_err(dqkv.float(), x.grad) < tol
     assert rel_err(dqw, qwd.grad) < 1e-4 and rel_err(dkw, kwd.grad) < 1e-4
+    if dtype == torch.bfloat16:
+        q0, k0, v0 = (t.reshape(B, L, H, 64) for t in qkv.chunk(3, -1))
+        eb.assert_within(outs["Q"], 0.25 * qn.detach().permute(0, 2, 1, 3), eb.rmsnorm_heads(q0, qw, 1e-5, 0.25).permute(0, 2, 1, 3), "Q, train outputs")
+        eb.assert_within(outs["K"], kn.detach().permute(0, 2, 1, 3), eb.rmsnorm_heads(k0, kw, 1e-5).permute(0, 2, 1, 3), "K, train outputs")
+        eb.assert_within(outs["V"], v0.double().permute(0, 2, 1, 3), eb.rmsnorm_heads(v0, None, 1e-5).permute(0, 2, 1, 3), "V, train outputs")
+        tok = lambda t: t.permute(0, 2, 1, 3).reshape(B * L, C)                  # head-major [B, H, L, 64] -> token-major columns
+        bound = torch.cat([tok(eb.rmsnorm_heads_backward(q0.permute(0, 2, 1, 3), gq, qw, 1e-5)),
+                           tok(eb.rmsnorm_heads_backward(k0.permute(0, 2, 1, 3), gk, kw, 1e-5)),
+                           tok(eb.rmsnorm_heads_backward(v0.permute(0, 2, 1, 3), gv, None, 1e-5))], dim=1)
+        eb.assert_within(dqkv, x.grad, bound, "d(qkv) of the RMSNorm backward")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -497,6 +519,15 @@ def test_attention_backward_mfma_against_autograd(tune, nw, B, H, Lq, Lk, shared
         got_dq = got_dq.sum(0, keepdim=True)
     assert rel_err(got_dq, qh.grad) < 2e-2
     assert rel_err(dK.float(), kd.grad) < 2e-2 and rel_err(dV.float(), vd.grad) < 2e-2
+    dO_hm = _head_major(dO_tok, B, Lq, H)
+    for kind, (gq, gk, gv) in (("mfma", (got_dq, dK, dV)), ("fp32 arithmetic", (rQ.float().cpu().double().sum(0, keepdim=True) if shared else rQ, rK, rV))):
+        bq, bk, bv = eb.attention_backward(qh.detach(), kd.detach(), vd.detach(), dO_hm, 64 ** -0.5, p_bf16=kind == "mfma", shared=shared)
+        eb.assert_within(gq, qh.grad, bq, f"dQ {kind}")
+        eb.assert_within(gk, kd.grad, bk, f"dK {kind}")
+        eb.assert_within(gv, vd.grad, bv, f"dV {kind}")
+    bound, lse_bound = eb.attention_and_lse(qs, kd.detach(), vd.detach(), math.log(2.0))
+    eb.assert_within(out, o.detach(), bound, "forward")
+    eb.assert_within(lse, torch.logsumexp(sc.detach(), -1) / math.log(2.0), lse_bound, "lse")
 
 
 def _poisoned_tail(t):
@@ -545,6 +576,14 @@ def test_attention_kernels_never_use_what_lies_behind_their_operands(Lq, Lk):
     o = torch.einsum("bhqk,bhkd->bqhd", torch.softmax(sc, -1), vd).reshape(Lq, C)
     o.backward(dO_tok.double())
     assert rel_err(dQ.float(), qh.grad) < 2e-2 and rel_err(dK.float(), kd.grad) < 2e-2 and rel_err(dV.float(), vd.grad) < 2e-2
+    bound = eb.attention(qh.detach(), kd.detach(), vd.detach(), 64 ** -0.5)
+    eb.assert_within(out, o.detach(), bound, "forward, transposed V")       # against the STORED q (rounded once more than q_tok)
+    eb.assert_within(out_r, o.detach(), bound, "forward, row-major V")
+    eb.assert_within(lse, torch.logsumexp(sc.detach(), -1) / math.log(2.0), eb.attention_lse(qh.detach(), kd.detach(), 64 ** -0.5), "lse")
+    bq, bk, bv = eb.attention_backward(qh.detach(), kd.detach(), vd.detach(), _head_major(dO_tok, B, Lq, H), 64 ** -0.5)
+    eb.assert_within(dQ, qh.grad, bq, "dQ")
+    eb.assert_within(dK, kd.grad, bk, "dK")
+    eb.assert_within(dV, vd.grad, bv, "dV")
 
 
 @pytest.mark.parametrize("dtype", DT)

@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+import error_bounds as eb
 from conftest import rel_err, vt_layout
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +47,7 @@ def test_gemm_plain(dtype, M, N, K):
     assert rel_err(out.float(), ref) < TOL[dtype]
     if dtype == torch.bfloat16:          # element-wise: bf16 rounding of an (almost) exact fp32 sum
         assert torch.allclose(out.float().cpu(), ref.float(), rtol=2 ** -7, atol=2 ** -9 * float(ref.abs().max()))
+        eb.assert_within(out, ref, eb.gemm(a, w, z=ref), "gemm")
 
 
 def test_gemm_transpose_detecting():
@@ -118,10 +120,13 @@ def test_gemm_bf16_residual_stream(tune, variant, M, N):
     out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(ad, wd, out, bias=bd, residual=res.to(DEV), res_rows=M // groups)
     assert rel_err(out.float(), prod + res.double().repeat(groups, 1)) < 4e-3
+    eb.assert_within(out, prod + res.double().repeat(groups, 1), eb.gemm(a, w, z=prod, bias=bias, residual=res.repeat(groups, 1)),
+                     "bf16 out, fp32 residual")
     x0 = _q(_rand((M, N), 85), dtype)
     x = x0.to(dtype).to(DEV)
     ops.gemm(ad, wd, x, bias=bd, residual=x)
     assert rel_err(x.float(), prod + x0.double()) < 4e-3
+    eb.assert_within(x, prod + x0.double(), eb.gemm(a, w, z=prod, bias=bias, residual=x0), "bf16 stream in place")
     with pytest.raises(Exception):                     # a bf16 residual that is NOT the output would be read as fp32: rejected
         ops.gemm(ad, wd, out, residual=x)
 
@@ -145,6 +150,7 @@ def test_gemm_head_contraction_in_the_epilogue(M, N, K):
     g = 0.5 * v * (1 + torch.erf(v / math.sqrt(2.0)))
     ref = g @ w3.double().T + b3.double()
     assert rel_err(out, ref) < 2e-3
+    eb.assert_within(out, ref, eb.n3_head(a, w, bias, w3, b3, z=v), "fused n3 head")
     # the unfused path on the same operands (bf16 intermediate) agrees to bf16 rounding
     h2 = torch.empty((M, N), dtype=dtype, device=DEV)
     ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), h2, bias=bias.to(DEV), act=ACT_GELU)
@@ -163,6 +169,7 @@ def test_layernorm_bf16_input(rows, C, with_bias):
     ops.layernorm(x.to(torch.bfloat16).to(DEV), w.to(DEV), None if b is None else b.to(DEV), 1e-5, out)
     ref = torch.nn.functional.layer_norm(x.double(), (C,), w.double(), None if b is None else b.double(), 1e-5)
     assert rel_err(out.float(), ref) < 4e-3
+    eb.assert_within(out, ref, eb.layernorm(x, w, b, 1e-5), "layernorm of a bf16 row")
     with pytest.raises(Exception):
         ops.layernorm(x.to(torch.bfloat16).to(DEV), w.to(DEV), None, 1e-5, torch.empty((rows, C), dtype=torch.float32, device=DEV))
 
@@ -186,6 +193,8 @@ def test_gemm_every_schedule_forced(tune, variant, dtype, K):
     out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), out, bias=bias.to(DEV), act=ACT_GELU)
     assert rel_err(out.float(), g) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, g, eb.gemm(a, w, z=v, bias=bias, act=True), f"{variant} bias + gelu")
     # (2) gamma + broadcast residual + row remap, fp32 out
     gin, gout, off = 230, 233, 1
     out2 = torch.zeros((3 * 233, N), dtype=torch.float32, device=DEV)
@@ -226,6 +235,8 @@ def test_gemm_chunk_ring_many_tiles(tune, variant):
     out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(ad, wd, out, bias=bd, act=ACT_GELU)
     assert rel_err(out.float(), g) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, g, eb.gemm(a, w, z=v, bias=bias, act=True), f"{variant} bias + gelu, 320 tiles")
     x0 = _rand((M, N), 34)
     x = x0.clone().to(DEV)
     ops.gemm(ad, wd, x, bias=bd, residual=x)
@@ -278,6 +289,7 @@ def test_gemm_ring_edge_shapes(tune, variant, M, N, K):
     out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(ad, wd, out)
     assert rel_err(out.float(), ref) < TOL[dtype]
+    eb.assert_within(out, ref, eb.gemm(a, w, z=ref), f"{variant} plain")
     x0 = _rand((M, N), 53)
     x = x0.clone().to(DEV)
     ops.gemm(ad, wd, x, residual=x)
@@ -297,6 +309,9 @@ def test_gemm_ring_kernels_are_race_free(tune, variant, M, N, K):
     tune("M324_GEMM", "v2")
     ref = torch.empty((M, N), dtype=dtype, device=DEV)
     ops.gemm(a, w, ref)
+    ref64 = a.double().cpu() @ w.double().cpu().T           # the anchor of the bit-identity chain, element by element
+    eb.assert_within(ref, ref64, eb.gemm(a, w, z=ref64), "v2, what the forty launches must equal")
+    del ref64
     tune("M324_GEMM", variant)
     outs = [torch.empty((M, N), dtype=dtype, device=DEV) for _ in range(4)]
     for it in range(40):
@@ -346,9 +361,12 @@ def test_gemm_v15_hand_placed_stream_equals_the_tile_kernels(tune, M, N, mode):
         v = rowstat[:, :1].double().cpu() * v + rowstat[:, 1:2].double().cpu() * colsum.double().cpu()
     if bias is not None:
         v = v + bias.double().cpu()
+    bound = eb.gemm(a, w, z=v, bias=bias, fold=(rowstat[:, 0], rowstat[:, 1], colsum) if "fold" in mode else None,
+                    act="gelu" in mode)
     if "gelu" in mode:
         v = 0.5 * v * (1 + torch.erf(v / math.sqrt(2.0)))
     assert rel_err(out[:M].float(), v) < TOL[dtype]
+    eb.assert_within(out[:M], v, bound, f"v15 {mode}")
 
 
 def test_gemm_v15_is_chosen_where_it_was_measured_faster_and_only_there(tune):
@@ -404,6 +422,10 @@ def test_gemm_v15_is_race_free_and_streams_large_outputs(tune, M):
     tune("M324_GEMM", "v2")
     ref = torch.empty((M, N), dtype=dtype, device=DEV)
     ops.gemm(a, w, ref, bias=bias, act=ACT_GELU)
+    if M < 20000:        # the anchor of the bit-identity chain, at the model's shape (M = 65536: 1.6 GB per fp64 matrix on the host)
+        z = a.double().cpu() @ w.double().cpu().T + bias.double().cpu()
+        eb.assert_within(ref, eb.gelu(z), eb.gemm(a, w, z=z, bias=bias, act=True), "v2, what the forty launches must equal")
+        del z
     tune("M324_GEMM", "v15")
     outs = [torch.empty((M, N), dtype=dtype, device=DEV) for _ in range(2)]
     for it in range(40 if M < 20000 else 12):
@@ -427,6 +449,7 @@ def test_gemm_skinny_rows(M, N, K):
     out = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), out, bias=bias.to(DEV), act=ACT_GELU)
     assert rel_err(out.float(), g) < TOL[dtype]
+    eb.assert_within(out, g, eb.gemm(a, w, z=v, bias=bias, act=True), "skinny bias + gelu")
     out2 = torch.zeros((M + 3, N), dtype=torch.float32, device=DEV)
     ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), out2, bias=bias.to(DEV), gamma=gamma.to(DEV), residual=res.to(DEV),
              row_map=(M, M, 3))
@@ -452,6 +475,9 @@ def test_gemm_training_aux_operand(dtype, M, N, K):
     z = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), g, bias=bias.to(DEV), act=ACT_GELU, preact_out=z)
     assert rel_err(z.float(), zref) < TOL[dtype] and rel_err(g.float(), gref) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(z, zref, eb.gemm(a, w, z=zref, bias=bias), "stored pre-activation")
+        eb.assert_within(g, gref, eb.gemm(a, w, z=zref, bias=bias, act=True), "gelu next to the stored pre-activation")
     # backward form: dz = (dy @ W2) * gelu'(z) with z as stored above
     dy = _q(_rand((M, K), 34), dtype)
     zs = z.float().cpu().double()
@@ -461,6 +487,8 @@ def test_gemm_training_aux_operand(dtype, M, N, K):
     dz = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(dy.to(dtype).to(DEV), w.to(dtype).to(DEV), dz, gelu_grad_of=z)
     assert rel_err(dz.float(), dref) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(dz, dref, eb.gemm_mul_gelu_grad(dy, w, zs), "product with gelu' of the stored pre-activation")
     with pytest.raises(M324Error):          # the pre-activation output needs an activation
         ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), g, preact_out=z)
     # the same pair with erf evaluated once (ABI 22): M324_AUX_STORE_GELU_GRAD leaves gelu'(z) of the fp32 z next to gelu(z), M324_AUX_MUL multiplies
@@ -471,9 +499,14 @@ def test_gemm_training_aux_operand(dtype, M, N, K):
     cdf0 = 0.5 * (1 + torch.erf(zref / math.sqrt(2.0)))
     pdf0 = torch.exp(-0.5 * zref * zref) / math.sqrt(2 * math.pi)
     assert rel_err(d.float(), cdf0 + zref * pdf0) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(d, cdf0 + zref * pdf0, eb.gemm_gelu_grad_store(a, w, z=zref, bias=bias), "stored gelu'(z)")
     dz2 = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
     ops.gemm(dy.to(dtype).to(DEV), w.to(dtype).to(DEV), dz2, mul_by=d)
     assert rel_err(dz2.float(), (dy.double() @ w.double().T) * d.float().cpu().double()) < TOL[dtype]
+    if dtype == torch.bfloat16:
+        eb.assert_within(dz2, (dy.double() @ w.double().T) * d.float().cpu().double(), eb.gemm(dy, w, gamma=d.float().cpu().double()),
+                         "product with the stored gelu'(z)")
     assert rel_err(dz2.float(), (dy.double() @ w.double().T) * (cdf0 + zref * pdf0)) < 2 * TOL[dtype]
     with pytest.raises(M324Error):
         ops.gemm(a.to(dtype).to(DEV), w.to(dtype).to(DEV), g, gelu_grad_out=d)
@@ -553,12 +586,18 @@ def test_gemm_qkv_heads_epilogue(B, L, H, norm, bias):
     for got, ref in ((Q, q), (Kk, k), (V, v)):
         assert torch.isfinite(got.float()).all()
         assert rel_err(got.float(), ref) < 4e-3
+    for i, (got, ref, nw, sc_) in enumerate(((Q, q, qw, ops.Q_PRESCALE), (Kk, k, kw, 1.0), (V, v, None, 1.0))):
+        bound = eb.qkv_heads(x, w[i * C:(i + 1) * C], bias=b[i * C:(i + 1) * C] if bias else None, norm_w=nw, eps=1e-5, scale=sc_)
+        eb.assert_within(got, ref, bound.reshape(B, L, H, 64).permute(0, 2, 1, 3), "QKV"[i])
     # attention on the fused outputs == attention on the two-pass outputs (up to one bf16 rounding of qkv in between)
     out_f = torch.empty((B * L, C), dtype=dtype, device=DEV)
     ops.attention(Q, Kk, V, out_f, prescaled=True, v_rowmajor=True)
     sc = torch.einsum("bhqd,bhkd->bhqk", q, k) * math.log(2.0)
     ref_o = torch.einsum("bhqk,bhkd->bqhd", torch.softmax(sc, dim=-1), v).reshape(B * L, C)
     assert rel_err(out_f.float(), ref_o) < 1e-2
+    Qc, Kc, Vc = (t.float().cpu() for t in (Q, Kk, V))                      # the attention itself, on the operands it read
+    eb.assert_within(out_f, _attn_ref(Qc, Kc, Vc, math.log(2.0)).reshape(B * L, C), eb.attention(Qc, Kc, Vc, math.log(2.0)),
+                     "attention on the fused outputs")
 
 
 @pytest.mark.parametrize("variant", [None, "v2", "v10", "v11", "v13"])
@@ -584,10 +623,28 @@ def test_gemm_qkv_heads_transposed_v_epilogue(tune, variant):
     ops.gemm(x, w, None, bias=b, qkv_heads=(Q, Kk, Vt, qw, kw, 1e-5, ops.Q_PRESCALE, L, H))
     assert torch.equal(Vt, Vt2)
     assert rel_err(Q.float(), Q2.float().double()) < 6e-3 and rel_err(Kk.float(), K2.float().double()) < 6e-3
+    y = x.double().cpu() @ w.double().cpu().T + b.double().cpu()
+    for i, (fused, two, nw, sc_) in enumerate(((Q, Q2, qw, ops.Q_PRESCALE), (Kk, K2, kw, 1.0), (Vt, Vt2, None, 1.0))):
+        r = y[:, i * C:(i + 1) * C].reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if nw is not None:
+            r = r * torch.rsqrt((r * r).mean(-1, keepdim=True) + 1e-5) * nw.double().cpu() * sc_
+        for got, two_pass in ((fused, False), (two, True)):
+            bound = eb.qkv_heads(x, w[i * C:(i + 1) * C], bias=b[i * C:(i + 1) * C], norm_w=nw, eps=1e-5, scale=sc_, two_pass=two_pass)
+            bound = bound.reshape(B, L, H, 64).permute(0, 2, 1, 3)
+            if i == 2:                                   # Vt: a permutation of V (L % 64 == 0: no padding)
+                eb.assert_within(got, vt_layout(r), vt_layout(bound), "Vt" + " two-pass" * two_pass)
+            else:
+                eb.assert_within(got, r, bound, "QK"[i] + " two-pass" * two_pass)
     out_f, out_2 = (torch.empty((B * L, C), dtype=dtype, device=DEV) for _ in range(2))
     ops.attention(Q, Kk, Vt, out_f, prescaled=True)
     ops.attention(Q2, K2, Vt2, out_2, prescaled=True)
     assert rel_err(out_f.float(), out_2.float().double()) < 1e-2
+    Vc = qkv[:, 2 * C:].float().cpu().reshape(B, L, H, 64).permute(0, 2, 1, 3)   # the row-major V behind Vt == Vt2 (pure data movement)
+    assert torch.equal(Vt.float().cpu(), vt_layout(Vc))
+    for got, Qc, Kc, name in ((out_f, Q, Kk, "fused"), (out_2, Q2, K2, "two-pass")):  # each attention on the operands it read
+        Qc, Kc = Qc.float().cpu(), Kc.float().cpu()
+        eb.assert_within(got, _attn_ref(Qc, Kc, Vc, math.log(2.0)).reshape(B * L, C), eb.attention(Qc, Kc, Vc, math.log(2.0)),
+                         f"attention on the {name} outputs, transposed V")
     from motion324_amd.lib import M324Error
     with pytest.raises(M324Error, match="64"):         # L = 200: a 32-token block would straddle the batches
         ops.gemm(x[:400], w, None, bias=b, qkv_heads=(Q[:, :, :200].contiguous(), Kk[:, :, :200].contiguous(),
@@ -615,6 +672,8 @@ def test_layernorm(dtype, C, with_bias, eps):
     ops.layernorm(x.to(DEV), w.to(DEV), None if b is None else b.to(DEV), eps, out)
     ref = torch.nn.functional.layer_norm(x.double(), (C,), w.double(), None if b is None else b.double(), eps)
     assert rel_err(out.float(), ref) < (1e-6 if dtype == torch.float32 else 4e-3)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.layernorm(x, w, b, eps), "layernorm, bf16 output")
 
 
 def test_layernorm_row_gather():
@@ -688,6 +747,11 @@ def test_qkv_split(dtype, B, L, H, norm):
     assert rel_err(K.float(), k.permute(0, 2, 1, 3)) < tol
     Q2, _, _ = ops.qkv_split(d[:, :C], None, None, qw.to(DEV) if norm else None, None, 1e-5, B, L, H, dtype, q_scale=0.25)
     assert rel_err(Q2.float(), 0.25 * q.permute(0, 2, 1, 3)) < tol        # power-of-two scale: same rounding
+    if dtype == torch.bfloat16:
+        q0, k0, _ = (t.reshape(B, L, H, 64) for t in qkv.chunk(3, dim=-1))
+        eb.assert_within(Q, q.permute(0, 2, 1, 3), eb.rmsnorm_heads(q0, qw if norm else None, 1e-5).permute(0, 2, 1, 3), "Q")
+        eb.assert_within(K, k.permute(0, 2, 1, 3), eb.rmsnorm_heads(k0, kw if norm else None, 1e-5).permute(0, 2, 1, 3), "K")
+        eb.assert_within(Q2, 0.25 * q.permute(0, 2, 1, 3), eb.rmsnorm_heads(q0, qw if norm else None, 1e-5, 0.25).permute(0, 2, 1, 3), "Q, scaled")
     Lp = (L + 63) // 64 * 64
     assert Vt.shape == (B, H, 64, Lp)
     assert torch.equal(Vt.float().cpu(), vt_layout(v.permute(0, 2, 1, 3).float()))   # pure data movement: exact
@@ -711,6 +775,8 @@ def test_attention(dtype, B, H, Lq, Lk):
     ref = _attn_ref(q, k, v, 64 ** -0.5).reshape(B * Lq, H * 64)
     assert torch.isfinite(out.float()).all()
     assert rel_err(out.float(), ref) < (1e-5 if dtype == torch.float32 else 8e-3)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.attention(q, k, v, 64 ** -0.5), "attention")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -727,6 +793,8 @@ def test_attention_prescaled_q(dtype, B, H, Lq, Lk):
     sc = torch.einsum("bhqd,bhkd->bhqk", qs.double(), k.double()) * math.log(2.0)     # exp2(x) = exp(x ln 2)
     ref = torch.einsum("bhqk,bhkd->bqhd", torch.softmax(sc, dim=-1), v.double()).reshape(B * Lq, H * 64)
     assert rel_err(out.float(), ref) < (1e-5 if dtype == torch.float32 else 8e-3)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.attention(qs, k, v, math.log(2.0)), "attention, prescaled q")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -748,6 +816,8 @@ def test_attention_lazy_max_growth(dtype):
     assert torch.isfinite(out.float()).all()
     assert rel_err(out.float(), ref) < (1e-5 if dtype == torch.float32 else 8e-3)
     assert rel_err(out.float()[5], ref[5]) < (1e-5 if dtype == torch.float32 else 1e-2)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.attention(q, k, v, 64 ** -0.5), "attention, growing scores")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -760,6 +830,8 @@ def test_attention_shared_q(dtype):
     ops.attention(q.to(dtype).to(DEV), k.to(dtype).to(DEV), vt_layout(v).to(dtype).to(DEV), out, shared_q=True)
     ref = _attn_ref(q.expand(T, -1, -1, -1), k, v, 64 ** -0.5).reshape(T * Lq, H * 64)
     assert rel_err(out.float(), ref) < (1e-5 if dtype == torch.float32 else 8e-3)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.attention(q, k, v, 64 ** -0.5), "attention, shared q")
 
 
 @pytest.mark.parametrize("T,H,Lq,Lk", [(8, 3, 2048, 64), (4, 2, 700, 64), (6, 1, 513, 37), (32, 12, 2048, 64)])
@@ -788,6 +860,10 @@ def test_attention_shared_q_frame_loop(tune, T, H, Lq, Lk):
     assert torch.isfinite(outs[0].float()).all()
     assert rel_err(outs[0].float(), ref) < 8e-3
     assert (lses[0].double().cpu() - torch.logsumexp(sc * math.log(2.0), dim=-1) / math.log(2.0)).abs().max() < 2e-3
+    bound, lse_bound = eb.attention_and_lse(qs, k, v, math.log(2.0))
+    eb.assert_within(outs[0], ref, bound, "attention, frame loop")
+    eb.assert_within(lses[0], torch.logsumexp(sc * math.log(2.0), dim=-1) / math.log(2.0), lse_bound, "lse, frame loop")
+    del bound, lse_bound
     assert torch.equal(outs[0], outs[1])
     assert torch.equal(lses[0], lses[1])
 
@@ -804,6 +880,8 @@ def test_attention_online_softmax_rescale(dtype):
     ref = _attn_ref(q, k, v, 64 ** -0.5).reshape(L, 64)
     assert rel_err(out.float(), ref) < (1e-5 if dtype == torch.float32 else 8e-3)
     assert rel_err(out.float()[7], ref[7]) < (1e-5 if dtype == torch.float32 else 8e-3)
+    if dtype == torch.bfloat16:
+        eb.assert_within(out, ref, eb.attention(q, k, v, 64 ** -0.5), "attention, late dominant key")
 
 
 @pytest.mark.parametrize("sched", ["nw4", "nw8"])
@@ -830,6 +908,9 @@ def test_attention_long_sequence_schedules(tune, sched, Lq, Lk, odd):
     assert rel_err(out.float()[9], ref[9]) < 1e-2
     lse_ref = torch.logsumexp(sc * math.log(2.0), dim=-1) / math.log(2.0)
     assert float((lse.cpu().double() - lse_ref).abs().max()) < 2e-2
+    bound, lse_bound = eb.attention_and_lse(qs, k, v, math.log(2.0))
+    eb.assert_within(out, ref, bound, f"attention {sched}")
+    eb.assert_within(lse, lse_ref, lse_bound, f"lse {sched}")
 
 
 @pytest.mark.parametrize("B,H,Lq,Lk", [(1, 2, 2048, 512), (1, 2, 2100, 2048), (1, 2, 2304, 1088), (2, 3, 2049, 576), (1, 1, 4096, 64 * 37),
@@ -869,6 +950,10 @@ def test_attention_one_wave_per_simd_stream(tune, B, H, Lq, Lk, spike):
     lse_ref = torch.logsumexp(sc * math.log(2.0), dim=-1) / math.log(2.0)
     assert float((lse.double() - lse_ref).abs().max()) < 2e-2
     assert rel_err(out, res["0"][0]) < 6e-3                       # same mathematics, different summation order
+    bound, lse_bound = eb.attention_and_lse(qs, k, v, math.log(2.0))
+    for pwg in ("1", "0"):
+        eb.assert_within(res[pwg][0], ref, bound, f"attention, M324_ATTN_PWG={pwg}")
+        eb.assert_within(res[pwg][1], lse_ref, lse_bound, f"lse, M324_ATTN_PWG={pwg}")
 
 
 @pytest.mark.parametrize("B,H,Lq,Lk,amp", [(1, 2, 2048, 512, 1.5), (1, 2, 2100, 2048, 1.5), (2, 3, 2049, 576, 2.2), (1, 1, 4096, 64 * 37, 1.0),
@@ -899,6 +984,10 @@ def test_attention_bounded_scores_stream(tune, B, H, Lq, Lk, amp):
     assert rel_err(out, ref) < 8e-3
     assert float((lse.double() - lse_ref).abs().max()) < 2e-2
     assert rel_err(out, res[False][0]) < 6e-3
+    bound, lse_bound = eb.attention_and_lse(qs, k, v, math.log(2.0))
+    for bounded in (True, False):
+        eb.assert_within(res[bounded][0], ref, bound, f"attention, bounded={bounded}")
+        eb.assert_within(res[bounded][1], lse_ref, lse_bound, f"lse, bounded={bounded}")
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -937,6 +1026,9 @@ def test_attention_merge_of_key_parts_equals_attention_over_all_keys(dtype, B, H
     assert torch.isfinite(got).all()
     assert rel_err(got, ref) < tol and rel_err(got[7], ref[7]) < 1.5 * tol
     assert rel_err(got, whole.float().cpu()) < (6e-3 if dtype == torch.bfloat16 else 5e-6)
+    if dtype == torch.bfloat16:
+        eb.assert_within(got, ref, eb.attention_merge(qs, k, v, math.log(2.0), cuts), "merged key parts")
+        eb.assert_within(whole, ref, eb.attention(qs, k, v, math.log(2.0)), "one attention over all keys")
     with pytest.raises(Exception):
         ops.attention_merge(parts[:1], out, B, H, Lq)
 
@@ -969,6 +1061,7 @@ def test_attention_row_major_v(B, H, Lq, Lk):
     ref = _attn_ref(q, k, v, 64 ** -0.5).reshape(B * Lq, H * 64)
     assert torch.isfinite(out_r.float()).all()
     assert rel_err(out_r.float(), ref) < 8e-3
+    eb.assert_within(out_r, ref, eb.attention(q, k, v, 64 ** -0.5), "attention, row-major V")
     assert torch.equal(out_r, out_t)                       # identical arithmetic, different operand layout
 
 
@@ -998,6 +1091,10 @@ def test_patchify(dtype, Hin):
     ref = torch.nn.functional.unfold(img, kernel_size=patch, stride=patch).transpose(1, 2).reshape(Fr * 256, 588)
     assert rel_err(out[:, :588], ref) < (2e-6 if dtype == torch.float32 else 4e-3)
     assert float(out[:, 588:].abs().max()) == 0.0
+    if dtype == torch.bfloat16:
+        img64 = torch.nn.functional.interpolate(video.double().permute(0, 3, 1, 2), (size, size), mode="bilinear", align_corners=False)
+        ref64 = torch.nn.functional.unfold((img64 - mean.double()) / std.double(), kernel_size=patch, stride=patch).transpose(1, 2)
+        eb.assert_within(out[:, :588], ref64.reshape(Fr * 256, 588), eb.patchify(ref64.reshape(Fr * 256, 588), Hin), "patch rows")
 
 
 # ------------------------------------------------------------------------------------------- points
@@ -1013,6 +1110,8 @@ def test_point_encode_and_concat(dtype):
     ref = torch.cat([proj.double().sin(), proj.double().cos(), xyz.double()], dim=1)
     assert rel_err(enc[:, :51], ref) < (1e-6 if dtype == torch.float32 else 4e-3)
     assert float(enc[:, 51:].abs().max()) == 0.0
+    if dtype == torch.bfloat16:
+        eb.assert_within(enc[:, :51], ref, eb.point_encode(proj, ref), "point features")
     feat = torch.full((P, Kp), 7.0, dtype=dtype, device=DEV)
     nrm, rgb = _rand((P, 3), 33), torch.rand((P, 3), generator=g)
     ops.point_concat(nrm.to(DEV), rgb.to(DEV), feat, C)
@@ -1125,6 +1224,9 @@ def test_gemm_ln_fold_producer(tune, variant, out_dtype, M, N, K, groups):
         exact = a.double() @ w.double().T + bias.double() + res.to(dtype).double()
         ops.gemm(ad, wd, out, bias=bias.to(DEV), residual=out, stats_out=part)
     assert rel_err(out.float(), exact) < (1e-5 if out_dtype == torch.float32 else 4e-3)
+    if out_dtype == torch.bfloat16:
+        prod = a.double() @ w.double().T + bias.double()
+        eb.assert_within(out, exact, eb.gemm(a, w, z=prod, bias=bias, residual=exact - prod), "the bf16 stream a producer leaves")
     if copy is not None:
         assert torch.equal(copy.cpu(), out.cpu().to(torch.bfloat16))         # the twin is the stored value, rounded once
     p = part.double().cpu()
@@ -1256,6 +1358,10 @@ def test_gemm_ln_fold_consumer_merges_block_table(tune, variant, M, N, K):
     assert torch.isfinite(outs[1]).all()
     assert rel_err(outs[1], ref) < 5e-3
     assert rel_err(outs[1], outs[0]) < 2e-4                  # bf16 outputs: a last-bit flip here and there
+    st = stat.double().cpu()
+    zf = st[:, :1] * (xb.double() @ wf.double().T) + st[:, 1:2] * colsum.double() + bias.double()
+    eb.assert_within(outs[0], eb.gelu(zf), eb.gemm(xb, wf, z=zf, bias=bias, fold=(st[:, 0], st[:, 1], colsum), act=True),
+                     "consumer epilogue on the merged table")
 
 
 @pytest.mark.parametrize("M,N,K", [(513, 3072, 768), (1100, 768, 1024)])
@@ -1322,6 +1428,10 @@ def test_gemm_ln_fold_consumer(tune, variant, mode, M, N, K):
         ref = 0.5 * ref * (1 + torch.erf(ref / math.sqrt(2.0)))
     # W' is rounded to bf16 (2^-9 per weight, averaging out over K) and the output once more
     assert rel_err(out.float(), ref) < (3e-3 if odt == torch.float32 else 5e-3)
+    st = stat.double().cpu()                                 # the epilogue's own arithmetic on the operands it reads
+    zf = st[:, :1] * (xb.double() @ wf.double().T) + st[:, 1:2] * colsum.double() + bias.double()
+    eb.assert_within(out, eb.gelu(zf) if mode == "gelu" else zf,
+                     eb.gemm(xb, wf, z=zf, bias=bias, fold=(st[:, 0], st[:, 1], colsum), act=mode == "gelu", out_dtype=odt), f"consumer epilogue {mode}")
 
 
 @pytest.mark.parametrize("L,vt", [(257, False), (324, False), (256, True)])
@@ -1351,6 +1461,17 @@ def test_gemm_ln_fold_qkv_heads(L, vt):
     want = run(h, w.to(torch.bfloat16), b, None)
     for g, r in zip(got, want):
         assert torch.isfinite(g).all() and rel_err(g, r) < 8e-3     # two bf16 roundings apart (h vs W')
+    st = stat.double().cpu()                                 # the epilogue's own arithmetic on the operands it reads
+    zf = st[:, :1] * (xb.double() @ wf.double().T) + st[:, 1:2] * colsum.double() + bias.double()
+    for i, (g, nw, sc_) in enumerate(zip(got, (qw, kw, None), (ops.Q_PRESCALE, 1.0, 1.0))):
+        r = zf[:, i * C:(i + 1) * C].reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if nw is not None:
+            r = r * torch.rsqrt((r * r).mean(-1, keepdim=True) + 1e-5) * nw.double() * sc_
+        bound = eb.qkv_heads(xb, wf[i * C:(i + 1) * C], bias=bias[i * C:(i + 1) * C], fold=(st[:, 0], st[:, 1], colsum[i * C:(i + 1) * C]),
+                             norm_w=nw, eps=1e-5, scale=sc_).reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if i == 2 and vt:
+            r, bound = vt_layout(r), vt_layout(bound)
+        eb.assert_within(g, r, bound, "QKV"[i] + " behind a folded LayerNorm")
     # C = 192 is three blocks: m324_gemm takes even block counts only -- the per-block table goes through the launch of its own
     with pytest.raises(Exception, match="even count"):
         run(xb, wf, bias, (_block_table(xb).to(DEV), colsum.to(DEV), 1e-5))
@@ -1376,6 +1497,10 @@ def test_gemm_ln_fold_n3_head():
     v = _ln_ref(xb.float(), lnw, lnb, 1e-5) @ w.double().T + b.double()
     v = 0.5 * v * (1 + torch.erf(v / math.sqrt(2.0)))
     assert rel_err(out, v @ w3.double().T + b3.double()) < 3e-3
+    st = stat.double().cpu()                                 # the epilogue's own arithmetic on the operands it reads
+    zf = st[:, :1] * (xb.double() @ wf.double().T) + st[:, 1:2] * colsum.double() + bias.double()
+    eb.assert_within(out, eb.gelu(zf) @ w3.double().T + b3.double(), eb.n3_head(xb, wf, bias, w3, b3, z=zf, fold=(st[:, 0], st[:, 1], colsum)),
+                     "n3 head behind a folded LayerNorm")
     # the same with the consumer merging the per-block table itself
     part2 = torch.empty((C // 64, M, 3), device=DEV)
     ops.gemm(xb.to(DEV), wf.to(DEV), None, bias=bias.to(DEV), act=ACT_GELU, n3=(w3.to(DEV), part2),
@@ -1429,3 +1554,14 @@ def test_gemm_cross_attention_projection_heads(B, L):
     ops.gemm(x, wkv, None, bias=bkv, qkv_heads=(None, Kf, Vtf, None, kw, 1e-5, 1.0, L, H, True))
     assert torch.isfinite(Kf.float()).all() and rel_err(Kf.float(), Ks.float().double()) < 6e-3
     assert torch.equal(Vtf, Vts)
+    for name, fused, two, wm, bv, nw, sc_ in (("Q", Qf, Qs, wq, bq, qw, ops.Q_PRESCALE), ("K", Kf, Ks, wkv[:C], bkv[:C], kw, 1.0),
+                                              ("Vt", Vtf, Vts, wkv[C:], bkv[C:], None, 1.0)):
+        r = (x.double().cpu() @ wm.double().cpu().T + bv.double().cpu()).reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if nw is not None:
+            r = r * torch.rsqrt((r * r).mean(-1, keepdim=True) + 1e-5) * nw.double().cpu() * sc_
+        for got, two_pass in ((fused, False), (two, True)):
+            bound = eb.qkv_heads(x, wm, bias=bv, norm_w=nw, eps=1e-5, scale=sc_, two_pass=two_pass).reshape(B, L, H, 64).permute(0, 2, 1, 3)
+            if name == "Vt":
+                eb.assert_within(got, vt_layout(r), vt_layout(bound), name + " two-pass" * two_pass)
+            else:
+                eb.assert_within(got, r, bound, name + " two-pass" * two_pass)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import error_bounds
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -258,6 +260,15 @@ def test_gemm_mx_qkv_heads_epilogue(L, vt):
     qref, kref, vref = rms(heads[0], qn) * scale, rms(heads[1], kn), heads[2]
     for got, ref in ((Q, qref), (Kh, kref)):
         assert torch.allclose(got.double().cpu(), ref, rtol=2 ** -7, atol=1e-3 * float(ref.abs().max()))
+    # element-wise error bounds: the operands are the DEQUANTISED values, so the bf16 GEMM's builder applies unchanged
+    da, dw = torch.from_numpy(deq(qa, sa)), torch.from_numpy(deq(qw, sw))
+    for i, (got, ref, nw, sc_) in enumerate(((Q, qref, qn, scale), (Kh, kref, kn, 1.0), (V, vref, None, 1.0))):
+        bound = error_bounds.qkv_heads(da, dw[i * C:(i + 1) * C], bias=bias[i * C:(i + 1) * C], norm_w=nw, eps=1e-5, scale=sc_)
+        bound = bound.reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if i == 2 and vt:
+            from conftest import vt_layout
+            ref, bound = vt_layout(ref), vt_layout(bound)
+        error_bounds.assert_within(got, ref, bound, "QKV"[i] + " of MXFP8 operands")
     if vt:
         # the transposed V with the documented key order (quarters 0, 2, 1, 3 of every 16 keys: conftest.vt_layout), element by element
         from conftest import vt_layout
