@@ -1079,16 +1079,79 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
 // attention_pwg.hip: one wave per SIMD, hand-placed instruction stream (long sequences, pre-scaled Q, transposed zero-padded Vt)
 void m324_attn_pwg_launch(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B, int H, int Lq, int Lk,
                           float* lse, bool bounded, hipStream_t s);
-static bool use_pwg(bool prescaled, bool vrow, bool nq2, int fnw, int Lq, int Lk) {
-    return m324::tunable(m324::TUN_ATTN_PWG) != 0 && prescaled && !vrow && !nq2 && fnw == 0 && Lq >= 2048 && Lk >= 512;
+
+// What one m324_attention call launches.  attn_plan() is the only place that fills it: m324_attention launches from it and
+// m324_attention_plan prints it.
+enum AttnFamily { ATTN_F32, ATTN_PWG, ATTN_PWG_BOUNDED, ATTN_FRAMES, ATTN_BF16 };
+struct AttnPlan {
+    AttnFamily family;
+    bool ps, vrow;               // ATTN_BF16: attn_bf16_kernel<PS, NQ, NW, VROW, NST>; ATTN_FRAMES: ps = nontemporal stores
+    int nq, nw, nst;
+    dim3 grid;
+    unsigned threads, lds_pad;
+    int nqt;                     // > 0: flat grid of nqt query tiles per (batch, head)
+};
+
+// flags: M324_ATTN_*, and 256 = the queries are shared by the batches (q_bstride == 0)
+static AttnPlan attn_plan(int B, int H, int Lq, int Lk, int flags, int dtype) {
+    AttnPlan p{};
+    p.nq = 1, p.nw = NW, p.nst = 3, p.threads = 256;
+    p.grid = dim3(ceil_div(Lq, QB), H, B);
+    if (dtype != M324_BF16) {
+        p.family = ATTN_F32;
+        return p;
+    }
+    const bool vrow = (flags & M324_ATTN_V_ROWMAJOR) != 0, ps = (flags & M324_ATTN_Q_PRESCALED) != 0;
+    // NQ = 2 (two query blocks per wave) measured slower than NQ = 1 on MI355X (254 VGPRs -> one wave per
+    // SIMD); it stays selectable for experiments only.
+    const bool nq2 = m324::tunable(m324::TUN_ATTN_NQ2) != 0 && Lq >= 1024 && !vrow;
+    // eight waves per workgroup for long query sets (M324_ATTN_NW=4|8 forces: A/B runs, tests)
+    const int fnw = m324::tunable(m324::TUN_ATTN_NW);
+    const bool w8 = !nq2 && (fnw ? fnw == 8 : (Lq >= 2048 && Lk >= 512));
+    // M324_ATTN_PWG=0: the eight-wave kernel below (A/B runs, tests)
+    if (m324::tunable(m324::TUN_ATTN_PWG) != 0 && ps && !vrow && !nq2 && fnw == 0 && Lq >= 2048 && Lk >= 512) {
+        p.family = (flags & M324_ATTN_SCORES_BOUNDED) ? ATTN_PWG_BOUNDED : ATTN_PWG;
+        p.grid = dim3((unsigned)((long)ceil_div(Lq, 256) * H * B));      // (m324_attention checks that it fits)
+        return p;
+    }
+    p.family = ATTN_BF16, p.ps = ps, p.vrow = vrow, p.nq = nq2 ? 2 : 1, p.nw = w8 ? 8 : 4, p.threads = p.nw * 64;
+    p.grid.x = ceil_div(Lq, (nq2 || w8) ? 2 * QB : QB);
+    // XCD-aware flat grid for the 8-wave kernel (M324_ATTN_FLAT=0 keeps the 3-D grid: A/B runs)
+    // The same flat order for the short sequences with several query tiles per (batch, head) -- the per-frame blocks:
+    // 324 / 257 tokens = 3 tiles of 128 queries that walk the SAME K / V.  On the 3-D grid they are consecutive
+    // workgroup ids, i.e. they land on three different XCDs and each pulls the head's K / V through its own L2
+    // (round 2 counters: 111.8 MB moved for 55.8 MB algorithmic); on the flat grid they are neighbours in ONE XCD's
+    // list.  M324_ATTN_FLAT=2 restricts the flat grid to the 8-wave kernel again (A/B runs).
+    const int flat = m324::tunable(m324::TUN_ATTN_FLAT);
+    const bool one_tile = ps && !w8 && !nq2 && !vrow && Lk <= KV;
+    if (flat != 0 && (w8 || (flat != 2 && !nq2 && !one_tile && p.grid.x > 1 && (long)p.grid.x * H * B >= 512))) {
+        p.nqt = (int)p.grid.x;
+        p.grid = dim3(p.grid.x * H * B, 1, 1);
+    }
+    const int occ = m324::tunable(m324::TUN_ATTN_OCC), xfl = m324::tunable(m324::TUN_ATTN_EXP);
+    if (ps && !w8 && Lk > KV && Lk <= 16 * KV && occ != 3) {
+        // per-frame blocks (round 6; row-major V from the fused q|k|v epilogue or the training step's transposed Vt, pre-scaled q, four
+        // waves, a handful of key tiles): four workgroups per CU instead of three (two LDS stages, 128 registers); microbench, interleaved
+        // A/B on one box: L = 324 26.6 -> 24.5 us, L = 257 22.6 -> 21.2 us; M324_ATTN_OCC=3 keeps the three-stage form (A/B)
+        p.nst = 2;
+    } else if (one_tile && (flags & 256) && B % 2 == 0 && Lq >= 512 && !(xfl & 8)) {
+        // shared queries under several batches of one key tile (the decoder): two frames per workgroup (M324_ATTN_EXP bit 3: A/B;
+        // bit 4: plain stores)
+        p.family = ATTN_FRAMES, p.ps = !(xfl & 16);
+        p.grid.z = B / 2;
+    } else if (one_tile && occ != 1) {               // one tile (M324_ATTN_OCC=1: A/B)
+        p.nst = 1;
+    } else if (occ == 2) {
+        // Co-residency: the NQ = 1 kernel fits 3 workgroups per CU (168 VGPRs, 32 KiB LDS).  Interleaved A/B on
+        // MI355X: 3 per CU beats 2 per CU (422 vs 453 us on the 10 368-token global attention) even though the
+        // grid then ends in a partly filled round -- latency hiding wins over round quantisation.
+        // M324_ATTN_OCC=2 pads the LDS allocation to force two per CU (experiments only).
+        p.lds_pad = 24 * 1024;
+    }
+    return p;
 }
 
-// the per-frame attentions (row-major V from the fused q|k|v epilogue, pre-scaled q, four waves, a handful of key tiles): the
-// two-stage, four-per-CU instantiation
-static bool two_stage(bool vrow, bool prescaled, bool w8, int Lk) {
-    (void)vrow;                                   // both V layouts (the training step's per-frame blocks read the transposed Vt)
-    return prescaled && !w8 && Lk > KV && Lk <= 16 * KV && m324::tunable(m324::TUN_ATTN_OCC) != 3;
-}
+static constexpr int attn_key(bool ps, int nq, int nw, bool vrow, int nst) { return (int)ps | nq << 1 | nw << 3 | (int)vrow << 7 | nst << 8; }
 
 extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B,
                               int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, void* stream) {
@@ -1096,124 +1159,73 @@ extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, cons
     M324_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, "m324_attention: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
     M324_REQUIRE(ldo >= (long)H * 64, "m324_attention: ldo too small");
     M324_REQUIRE(H <= 65535 && B <= 65535, "m324_attention: grid too large");
+    M324_REQUIRE(!(q_prescaled & M324_ATTN_V_ROWMAJOR) || dtype == M324_BF16, "m324_attention: row-major V needs the bf16 kernel (transposing LDS reads)");
+    if (dtype != M324_BF16 && dtype != M324_F32) M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention: dtype %d", dtype);
+    M324_REQUIRE(dtype == M324_BF16 ? (ldo * 2) % 8 == 0 : ldo % 4 == 0, "m324_attention: ldo misaligned");
     const int Lkp = (Lk + 63) / 64 * 64;
-    dim3 grid(ceil_div(Lq, QB), H, B);
     hipStream_t s = (hipStream_t)stream;
-    const bool vrow = (q_prescaled & M324_ATTN_V_ROWMAJOR) != 0;
-    const bool bounded = (q_prescaled & M324_ATTN_SCORES_BOUNDED) != 0;
-    q_prescaled &= M324_ATTN_Q_PRESCALED;
-    M324_REQUIRE(!vrow || dtype == M324_BF16, "m324_attention: row-major V needs the bf16 kernel (transposing LDS reads)");
-    const float sl = q_prescaled ? 1.0f : scale * LOG2E;
-    if (dtype == M324_BF16) {
-        M324_REQUIRE((ldo * 2) % 8 == 0, "m324_attention: ldo misaligned");
-        // NQ = 2 (two query blocks per wave) measured slower than NQ = 1 on MI355X (254 VGPRs -> one wave per
-        // SIMD); it stays selectable for experiments only.
-        const bool nq2 = m324::tunable(m324::TUN_ATTN_NQ2) != 0 && Lq >= 1024 && !vrow;
-        // eight waves per workgroup for long query sets (M324_ATTN_NW=4|8 forces: A/B runs, tests)
-        const int fnw = m324::tunable(m324::TUN_ATTN_NW);
-        const bool w8 = !nq2 && (fnw ? fnw == 8 : (Lq >= 2048 && Lk >= 512));
-        if (use_pwg(q_prescaled != 0, vrow, nq2, fnw, Lq, Lk)) {        // M324_ATTN_PWG=0: the eight-wave kernel below (A/B runs, tests)
+    const float sl = (q_prescaled & M324_ATTN_Q_PRESCALED) ? 1.0f : scale * LOG2E;
+    const AttnPlan p = attn_plan(B, H, Lq, Lk, (q_prescaled & 7) | (q_bstride == 0 ? 256 : 0), dtype);
+    const int xfl = m324::tunable(m324::TUN_ATTN_EXP);
+#define M324_ATTN(PS, NQ, NWV, VROW, NST)                                                                               \
+    case attn_key(PS, NQ, NWV, VROW, NST):                                                                                   \
+        hipLaunchKernelGGL((attn_bf16_kernel<PS, NQ, NWV, VROW, NST>), p.grid, dim3(p.threads), p.lds_pad, s,           \
+                           (const bf16_t*)Q, q_bstride, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, \
+                           Lkp, sl, lse, p.nqt, xfl);                                                                    \
+        break
+    switch (p.family) {
+        case ATTN_F32:
+            hipLaunchKernelGGL(attn_f32_kernel, p.grid, dim3(p.threads), 0, s, (const float*)Q, q_bstride, (const float*)K,
+                               (const float*)Vt, (float*)O, ldo, H, Lq, Lk, Lkp, sl, lse);
+            break;
+        case ATTN_PWG:
+        case ATTN_PWG_BOUNDED:
             M324_REQUIRE((long)ceil_div(Lq, 256) * H * B < (1l << 31), "m324_attention: grid too large");
-            m324_attn_pwg_launch(Q, q_bstride, K, Vt, O, ldo, B, H, Lq, Lk, lse, bounded, s);
-            M324_CHECK_LAUNCH("m324_attention");
-            return M324_OK;
-        }
-        dim3 g2(ceil_div(Lq, nq2 ? 2 * QB : (w8 ? 2 * QB : QB)), H, B);
-        // XCD-aware flat grid for the 8-wave kernel (M324_ATTN_FLAT=0 keeps the 3-D grid: A/B runs)
-        // The same flat order for the short sequences with several query tiles per (batch, head) -- the per-frame blocks:
-        // 324 / 257 tokens = 3 tiles of 128 queries that walk the SAME K / V.  On the 3-D grid they are consecutive
-        // workgroup ids, i.e. they land on three different XCDs and each pulls the head's K / V through its own L2
-        // (round 2 counters: 111.8 MB moved for 55.8 MB algorithmic); on the flat grid they are neighbours in ONE XCD's
-        // list.  M324_ATTN_FLAT=2 restricts the flat grid to the 8-wave kernel again (A/B runs).
-        int nqt = 0;
-        const int flat = m324::tunable(m324::TUN_ATTN_FLAT);
-        const bool one_tile = q_prescaled && !w8 && !nq2 && !vrow && Lk <= KV;
-        if (flat != 0 && (w8 || (flat != 2 && !nq2 && !one_tile && g2.x > 1 && (long)g2.x * H * B >= 512))) {
-            nqt = (int)g2.x;
-            g2 = dim3(g2.x * H * B, 1, 1);
-        }
-        // Co-residency: the NQ = 1 kernel fits 3 workgroups per CU (168 VGPRs, 32 KiB LDS).  Interleaved A/B on
-        // MI355X: 3 per CU beats 2 per CU (422 vs 453 us on the 10 368-token global attention) even though the
-        // grid then ends in a partly filled round -- latency hiding wins over round quantisation.
-        // M324_ATTN_OCC=2 pads the LDS allocation to force two per CU (experiments only).
-        const unsigned pad = m324::tunable(m324::TUN_ATTN_OCC) == 2 ? 24 * 1024 : 0;
-        const int xfl = m324::tunable(m324::TUN_ATTN_EXP);
-#define M324_ATTN(PS, NQ, NWV)                                                                                          \
-    hipLaunchKernelGGL((attn_bf16_kernel<PS, NQ, NWV>), g2, dim3(NWV * 64), pad, s, (const bf16_t*)Q, q_bstride,         \
-                       (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, sl, lse, nqt, xfl)
-#define M324_ATTN_VR(PS, NWV)                                                                                            \
-    hipLaunchKernelGGL((attn_bf16_kernel<PS, 1, NWV, true>), g2, dim3(NWV * 64), pad, s, (const bf16_t*)Q, q_bstride,    \
-                       (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, sl, lse, nqt, xfl)
-        if (two_stage(vrow, q_prescaled != 0, w8, Lk)) {
-            // per-frame blocks (round 6): four workgroups per CU instead of three (two LDS stages, 128 registers); microbench, interleaved
-            // A/B on one box: L = 324 26.6 -> 24.5 us, L = 257 22.6 -> 21.2 us; M324_ATTN_OCC=3 keeps the three-stage form (A/B)
-            if (vrow)
-                hipLaunchKernelGGL((attn_bf16_kernel<true, 1, 4, true, 2>), g2, dim3(256), 0, s, (const bf16_t*)Q, q_bstride, (const bf16_t*)K,
-                                   (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, sl, lse, nqt, xfl);
-            else
-                hipLaunchKernelGGL((attn_bf16_kernel<true, 1, 4, false, 2>), g2, dim3(256), 0, s, (const bf16_t*)Q, q_bstride, (const bf16_t*)K,
-                                   (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, sl, lse, nqt, xfl);
-        } else if (vrow) {
-            if (q_prescaled) { if (w8) M324_ATTN_VR(true, 8); else M324_ATTN_VR(true, 4); }
-            else { if (w8) M324_ATTN_VR(false, 8); else M324_ATTN_VR(false, 4); }
-        } else if (q_prescaled && !w8 && !nq2 && !vrow && Lk <= KV && q_bstride == 0 && B % 2 == 0 && Lq >= 512 && !(xfl & 8)) {
-            // shared queries under several batches of one key tile (the decoder): two frames per workgroup (M324_ATTN_EXP bit 3: A/B)
-            if (xfl & 16)       // plain stores
-                hipLaunchKernelGGL((attn_frames_kernel<2, false>), dim3(ceil_div(Lq, QB), H, B / 2), dim3(256), 0, s, (const bf16_t*)Q,
+            m324_attn_pwg_launch(Q, q_bstride, K, Vt, O, ldo, B, H, Lq, Lk, lse, p.family == ATTN_PWG_BOUNDED, s);
+            break;
+        case ATTN_FRAMES:
+            if (p.ps)
+                hipLaunchKernelGGL((attn_frames_kernel<2, true>), p.grid, dim3(p.threads), 0, s, (const bf16_t*)Q,
                                    (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, lse);
             else
-                hipLaunchKernelGGL((attn_frames_kernel<2, true>), dim3(ceil_div(Lq, QB), H, B / 2), dim3(256), 0, s, (const bf16_t*)Q,
+                hipLaunchKernelGGL((attn_frames_kernel<2, false>), p.grid, dim3(p.threads), 0, s, (const bf16_t*)Q,
                                    (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, lse);
-        } else if (q_prescaled && !w8 && !nq2 && Lk <= KV && m324::tunable(m324::TUN_ATTN_OCC) != 1) {      // one tile (M324_ATTN_OCC=1: A/B)
-            hipLaunchKernelGGL((attn_bf16_kernel<true, 1, 4, false, 1>), g2, dim3(256), 0, s, (const bf16_t*)Q, q_bstride,
-                               (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, sl, lse, nqt, xfl);
-        } else if (q_prescaled) { if (nq2) M324_ATTN(true, 2, 4); else if (w8) M324_ATTN(true, 1, 8); else M324_ATTN(true, 1, 4); }
-        else { if (nq2) M324_ATTN(false, 2, 4); else if (w8) M324_ATTN(false, 1, 8); else M324_ATTN(false, 1, 4); }
-#undef M324_ATTN_VR
-#undef M324_ATTN
-    } else if (dtype == M324_F32) {
-        M324_REQUIRE(ldo % 4 == 0, "m324_attention: ldo misaligned");
-        hipLaunchKernelGGL(attn_f32_kernel, grid, dim3(256), 0, s, (const float*)Q, q_bstride, (const float*)K,
-                           (const float*)Vt, (float*)O, ldo, H, Lq, Lk, Lkp, sl, lse);
-    } else {
-        M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention: dtype %d", dtype);
+            break;
+        case ATTN_BF16:
+            switch (attn_key(p.ps, p.nq, p.nw, p.vrow, p.nst)) {      // the instantiations that are built
+                M324_ATTN(true, 1, 4, false, 3); M324_ATTN(true, 1, 8, false, 3); M324_ATTN(true, 2, 4, false, 3);
+                M324_ATTN(false, 1, 4, false, 3); M324_ATTN(false, 1, 8, false, 3); M324_ATTN(false, 2, 4, false, 3);
+                M324_ATTN(true, 1, 4, true, 3); M324_ATTN(true, 1, 8, true, 3);
+                M324_ATTN(false, 1, 4, true, 3); M324_ATTN(false, 1, 8, true, 3);
+                M324_ATTN(true, 1, 4, false, 2); M324_ATTN(true, 1, 4, true, 2);       // per-frame blocks
+                M324_ATTN(true, 1, 4, false, 1);                                       // one key tile
+                default:
+                    M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention: attn_bf16_kernel<%d, %d, %d, %d, %d> is not built", (int)p.ps, p.nq, p.nw,
+                              (int)p.vrow, p.nst);
+            }
+            break;
     }
+#undef M324_ATTN
     M324_CHECK_LAUNCH("m324_attention");
     return M324_OK;
 }
 
-// Name and grid (threads) of the kernel m324_attention would launch: see m324_gemm_plan.
+// Name and grid (threads) of the kernel m324_attention would launch: see m324_gemm_plan.  flags: attn_plan.  Returns 0 for the fp32
+// kernel, 4 for the hand-placed stream, otherwise the waves per workgroup.
 extern "C" int m324_attention_plan(int B, int H, int Lq, int Lk, int flags, int dtype, char* buf, int n) {
     M324_REQUIRE(buf && n > 0 && B > 0 && H > 0 && Lq > 0 && Lk > 0, "m324_attention_plan: bad arguments");
-    if (dtype != M324_BF16) {
-        snprintf(buf, (size_t)n, "attn_f32_kernel grid=%ldx%dx%d", (long)ceil_div(Lq, QB) * 256, H, B);
-        return 0;
+    const AttnPlan p = attn_plan(B, H, Lq, Lk, flags, dtype);
+    const char* tf[2] = {"false", "true"};
+    char name[96];
+    switch (p.family) {
+        case ATTN_F32: snprintf(name, sizeof(name), "attn_f32_kernel"); break;
+        case ATTN_PWG: snprintf(name, sizeof(name), "attn_pwg_kernel"); break;
+        case ATTN_PWG_BOUNDED: snprintf(name, sizeof(name), "attn_pwg_bounded_kernel"); break;
+        case ATTN_FRAMES: snprintf(name, sizeof(name), "attn_frames_kernel<2, %s>", tf[p.ps]); break;
+        case ATTN_BF16: snprintf(name, sizeof(name), "attn_bf16_kernel<%s, %d, %d, %s, %d>", tf[p.ps], p.nq, p.nw, tf[p.vrow], p.nst); break;
     }
-    const bool vrow = (flags & M324_ATTN_V_ROWMAJOR) != 0, ps = (flags & M324_ATTN_Q_PRESCALED) != 0;
-    const bool nq2 = m324::tunable(m324::TUN_ATTN_NQ2) != 0 && Lq >= 1024 && !vrow;
-    const int fnw = m324::tunable(m324::TUN_ATTN_NW);
-    const bool w8 = !nq2 && (fnw ? fnw == 8 : (Lq >= 2048 && Lk >= 512));
-    if (use_pwg(ps, vrow, nq2, fnw, Lq, Lk)) {
-        snprintf(buf, (size_t)n, "%s grid=%ldx1x1", (flags & M324_ATTN_SCORES_BOUNDED) ? "attn_pwg_bounded_kernel" : "attn_pwg_kernel",
-                 (long)ceil_div(Lq, 256) * H * B * 256);
-        return 4;
-    }
-    const long gx = ceil_div(Lq, (nq2 || w8) ? 2 * QB : QB);
-    const int nwv = w8 ? 8 : 4;
-    const int flat = m324::tunable(m324::TUN_ATTN_FLAT);
-    const bool one_tile = ps && !w8 && !nq2 && !vrow && Lk <= KV;
-    const int nst = two_stage(vrow, ps, w8, Lk) ? 2 : 3;
-    if (flat != 0 && (w8 || (flat != 2 && !nq2 && !one_tile && gx > 1 && gx * H * B >= 512)))
-        snprintf(buf, (size_t)n, "attn_bf16_kernel<%s, %d, %d, %s, %d> grid=%ldx1x1", ps ? "true" : "false", nq2 ? 2 : 1, nwv,
-                 vrow ? "true" : "false", nst, gx * H * B * nwv * 64);
-    else if (one_tile && (flags & 256) && B % 2 == 0 && Lq >= 512 && !(m324::tunable(m324::TUN_ATTN_EXP) & 8))
-        snprintf(buf, (size_t)n, "attn_frames_kernel<2, %s> grid=%ldx%dx%d", (m324::tunable(m324::TUN_ATTN_EXP) & 16) ? "false" : "true", gx * 256, H, B / 2);
-    else if (ps && !vrow && !w8 && !nq2 && Lk <= KV && m324::tunable(m324::TUN_ATTN_OCC) != 1)
-        snprintf(buf, (size_t)n, "attn_bf16_kernel<true, 1, 4, false, 1> grid=%ldx%dx%d", gx * nwv * 64, H, B);
-    else
-        snprintf(buf, (size_t)n, "attn_bf16_kernel<%s, %d, %d, %s, %d> grid=%ldx%dx%d", ps ? "true" : "false", nq2 ? 2 : 1, nwv,
-                 vrow ? "true" : "false", nst, gx * nwv * 64, H, B);
-    return nwv;
+    snprintf(buf, (size_t)n, "%s grid=%ldx%ux%u", name, (long)p.grid.x * p.threads, p.grid.y, p.grid.z);
+    return p.family == ATTN_F32 ? 0 : p.nw;
 }
 
 extern "C" int m324_attention_bwd_mfma(const void* Qs, const void* Qst, long q_bstride, long qt_bstride, const void* K,

@@ -1041,34 +1041,30 @@ static int xcd_mode(const m324_gemm_args* a) {
     return 1 | old_refetch;
 }
 
-// Kernel choice.  M324_GEMM=v1|v2|v5|v9|v10|v11|v12|v13|v15 forces a variant (A/B measurements, tests).  (v7, the half-tile ring
+// Kernel choice (pick_variant) and, around it, everything else one call launches (make_plan below).  The schedules:
+//    1  gemm_kernel         128 x 128, register staging, scalar stores: whatever the vectorised epilogue cannot address
+//    2  gemm_glds_kernel    128 x 128, LDS-DMA, two stages; the only batched one
+//    5  gemm_glds5_kernel   256 x 256, LDS-DMA, two stages (no LayerNorm fold)
+//    9  gemm_skinny_kernel  M <= 64, split-K over the eight waves
+//   10  gemm_ring_kernel    256 x 256 chunk ring, eight waves, persistent; the only one with the N3 epilogue
+//   11  gemm_ring4_kernel   256 x 256 chunk ring, four waves, persistent     (gemm_ring4.hip)
+//   12  gemm_ring3_kernel   256 x 128 chunk ring                             (gemm_ring4.hip)
+//   13  gemm_ring2_kernel   128 x 128 chunk ring
+//   15  gemm_hp_*_kernel    256 x 128 hand-placed K = 768 stream, persistent (gemm_hp.hip)
+// M324_GEMM=v1|v2|v5|v9|v10|v11|v12|v13|v15 forces one (A/B measurements, tests).  (v7, the half-tile ring
 // the chunk-ring kernels replaced, was retired in round 3: no shape reaches it -- K is a multiple of 64 for bf16 -- and its
 // A/B tables are kept in profiles/r01_ab_gemm_schedules.md.  v14, round 5's two persistent 256 x 128 workgroups per CU, was retired in
 // round 6: v15 took every shape it was chosen for (41.4 against 44.2 us at 10368 x 2304 x 768); tables: profiles/r05_gemm_labs.md section 2.)
 static int forced_variant() { return m324::tunable(m324::TUN_GEMM); }   // M324_GEMM at load / m324_set_tunable
 
-// v10 is persistent: one 8-wave workgroup per CU (160 KiB of LDS each); M324_GEMM_PERSIST=0: one workgroup per tile (A/B)
-static int ring_grid(long ntiles) {
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n - (n & 7);                                 // a multiple of 8: tile t and t + grid share an XCD
-    }();
-    if (m324::tunable(m324::TUN_GEMM_PERSIST) == 0 || n_cu <= 0) return (int)ntiles;
-    return (int)(ntiles < n_cu ? ntiles : n_cu);
-}
+// v10 and v15 are persistent on a multiple of 8 workgroups: tile t and t + grid share an XCD
+static int cus8() { const int n = m324::cu_count(); return n - (n & 7); }
 
 static Epilogue make_epilogue(const m324_gemm_args* a);
-// v15's epilogue code as gemm_hp.hip counts it: GELU bit 0, LayerNorm-fold consumer bit 3; -1: an epilogue it does not build
-static int hp_act(const m324_gemm_args* a) {
-    if (a->aux_mode != M324_AUX_NONE || (a->act != M324_ACT_NONE && a->act != M324_ACT_GELU)) return -1;
-    return (a->act == M324_ACT_GELU ? 1 : 0) | (a->ln_rowstat ? 8 : 0);
-}
-static int hp_res(const m324_gemm_args* a) { return (!a->residual && a->row_gin <= 0) ? 0 : 1; }
 static bool nbatch_one(const m324_gemm_args* a) { return a->batch <= 1; }
 
-static int pick_variant(const m324_gemm_args* a) {
+// actx: the epilogue's template code (make_plan); v15 builds four of them (hp_ok)
+static int pick_variant(const m324_gemm_args* a, int actx) {
     if (!vec_ok(a)) return 1;
     int f = forced_variant();
     if (f == 7) f = 0;                           // retired schedule: the chooser decides
@@ -1081,7 +1077,7 @@ static int pick_variant(const m324_gemm_args* a) {
     if (f == 14) f = 0;                          // retired schedule: the chooser decides
     // v15 (gemm_hp.hip): the hand-placed K = 768 stream with the deferred epilogue; hp_ok lists what it takes
     if (f == 15) {
-        if (ring_ok && nbatch_one(a) && m324::hp_ok(a, make_epilogue(a), hp_act(a), hp_res(a))) return 15;
+        if (ring_ok && nbatch_one(a) && m324::hp_ok(a, make_epilogue(a), actx, cus8())) return 15;
         f = 0;
     }
     if (a->M <= 64 && bf16 && !a->aux_mode && (f == 0 || f == 9)) return 9;
@@ -1101,9 +1097,9 @@ static int pick_variant(const m324_gemm_args* a) {
     // 0.770 -> 0.752 ms with the m324_rowstats_finish launch in front included (tools/block_lab.py, alternated processes)
     const long thp = (long)(a->N / 128) * ceil_div(a->M, BM5);
     const int hpm = m324::tunable(m324::TUN_HP);
-    if (f == 0 && ring_ok && nbatch_one(a) && hpm != 0 && a->K == 768 && a->N % 128 == 0 && thp >= 512 && hp_act(a) >= 0 &&
-        ((hp_act(a) & 1) ? ((hpm & 1) != 0 || ((hpm & 4) != 0 && thp >= 4096)) : (hpm & 2) != 0) &&
-        m324::hp_ok(a, make_epilogue(a), hp_act(a), hp_res(a)))
+    if (f == 0 && ring_ok && nbatch_one(a) && hpm != 0 && a->K == 768 && a->N % 128 == 0 && thp >= 512 &&
+        ((actx & 1) ? ((hpm & 1) != 0 || ((hpm & 4) != 0 && thp >= 4096)) : (hpm & 2) != 0) &&
+        m324::hp_ok(a, make_epilogue(a), actx, cus8()))
         return 15;
     const long t5 = (long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5);
     const double e5 = (double)t5 / (double)(((t5 + 255) / 256) * 256);
@@ -1135,24 +1131,6 @@ static int pick_variant(const m324_gemm_args* a) {
     return 2;
 }
 
-template <typename TOUT, int ACT, int RES>
-static int launch_pipe(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int variant) {
-    if (variant == 11 || variant == 12) return m324::launch_ring4(a, s, ep, ACT, RES, xcd_mode(a), variant);
-    if (variant == 13) {
-        hipLaunchKernelGGL((gemm_ring2_kernel<TOUT, ACT, RES>), dim3(ceil_div(a->N, BN) * ceil_div(a->M, BM)), dim3(256), 0, s,
-                           (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep,
-                           ceil_div(a->N, BN), xcd_mode(a));
-        return M324_OK;
-    }
-    if (variant == 10) {
-        hipLaunchKernelGGL((gemm_ring_kernel<TOUT, ACT, RES>), dim3(ring_grid(ceil_div(a->N, BN5) * ceil_div(a->M, BM5))), dim3(512), 0, s,
-                           (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep,
-                           ceil_div(a->N, BN5), xcd_mode(a));
-        return M324_OK;
-    }
-    M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: no pipelined kernel for schedule %d", variant);
-}
-
 static Epilogue make_epilogue(const m324_gemm_args* a) {
     return Epilogue{a->bias, a->gamma, a->residual, a->ldr, a->res_rows, a->act, a->row_gin, a->row_gout, a->row_off,
                     a->strideA, a->strideW, a->strideC, a->aux, a->ldaux, a->aux_mode,
@@ -1164,110 +1142,115 @@ static Epilogue make_epilogue(const m324_gemm_args* a) {
                     static_cast<bf16_t*>(a->ln_copy_out), a->ln_ldcopy, a->ln_rowstat ? a->ln_ncb : 0, a->ln_eps};
 }
 
+// The one description of a call: epilogue codes, schedule, kernel and grid.  m324_gemm launches from it, m324_gemm_plan prints it,
+// m324_gemm_pair asks it; nothing else decides any of the four.
+static GemmPlan make_plan(const m324_gemm_args* a) {
+    GemmPlan p{};
+    p.nbatch = a->batch > 1 ? a->batch : 1;
+    // (ACTX, RES): gemm_tile.h store_tile_lds.  RES: 0 none, 1 the output's own rows, 2 mapped rows (res_rows / row map)
+    const int res = !a->residual && a->row_gin <= 0 ? 0
+                    : (a->residual && a->row_gin <= 0 && (a->res_rows <= 0 || a->res_rows >= a->M)) ? 1 : 2;
+    const bool n3 = a->aux_mode == M324_AUX_N3;
+    if (n3) p.actx = 5;
+    else if (a->aux_mode == M324_AUX_QKV_HEADS || a->aux_mode == M324_AUX_QKV_HEADS_VT) p.actx = 4;
+    else if (a->aux_mode == M324_AUX_STORE_PREACT || a->aux_mode == M324_AUX_STORE_GELU_GRAD) p.actx = 2;
+    else if (a->aux_mode == M324_AUX_MUL_GELU_GRAD || a->aux_mode == M324_AUX_MUL) p.actx = 3;
+    else if (a->act == M324_ACT_GELU) p.actx = 1, p.res = res ? 2 : 0;
+    else p.res = res;
+    // LayerNorm fold (m324_gemm validated the combination: consumer XOR producer)
+    if (a->ln_rowstat) p.actx |= 8, p.res = 0;
+    else if (a->ln_stats_out || a->ln_copy_out) p.actx = a->out_dtype == M324_F32 ? 48 : 16, p.res = res;   // fp32 stream: statistics + bf16 twin
+
+    // N3 is built on the 256 x 256 chunk ring only (host-checked shape), a batch on v2 only
+    p.variant = n3 ? 10 : p.nbatch > 1 ? 2 : pick_variant(a, p.actx);
+
+    const long t128 = (long)ceil_div(a->N, BN) * ceil_div(a->M, BM), t256 = (long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5);
+    p.threads = 256, p.grid_y = 1;
+    switch (p.variant) {
+        case 1: p.name = "gemm_kernel"; p.wg = ceil_div(a->N, BN); p.grid_y = ceil_div(a->M, BM); break;
+        case 2: p.name = "gemm_glds_kernel"; p.wg = t128; p.grid_y = p.nbatch; break;
+        case 5: p.name = "gemm_glds5_kernel"; p.wg = t256; p.threads = 512; break;
+        case 9: p.name = "gemm_skinny_kernel"; p.wg = ceil_div(a->N, 32); p.threads = 512; p.actx = p.actx != 0; p.res = 0; break;   // <TOUT, GELU>
+        // one 8-wave workgroup per CU (160 KiB of LDS each); M324_GEMM_PERSIST=0: one workgroup per tile (A/B)
+        case 10: p.name = "gemm_ring_kernel"; p.wg = m324::tunable(m324::TUN_GEMM_PERSIST) == 0 || t256 < cus8() ? t256 : cus8(); p.threads = 512; break;
+        case 11: p.name = "gemm_ring4_kernel"; p.wg = t256 < m324::cu_count() ? t256 : m324::cu_count(); break;
+        case 12: p.name = "gemm_ring3_kernel"; p.wg = (long)ceil_div(a->N, 128) * ceil_div(a->M, BM5); break;
+        case 13: p.name = "gemm_ring2_kernel"; p.wg = t128; break;
+        default: p.name = "gemm_hp_kernel"; p.wg = (long)(a->N / 128) * ceil_div(a->M, BM5); if (p.wg > cus8()) p.wg = cus8(); break;   // 15
+    }
+    return p;
+}
+
+// The tile kernels (schedules 2, 5, 10 - 13) of one (ACTX, RES).  What is built: N3 (ACTX & 7 == 5) on the 256 x 256 chunk ring only;
+// the LayerNorm fold (bits 3, 4) for bf16 operands and not on v5; heads / N3 (bit 2), the folded GELU consumer (9) and the producer of a
+// bf16 stream (16) with a bf16 output, the producer of an fp32 stream (48) with an fp32 one; the chunk rings for bf16 operands.
+template <typename TIN, typename TOUT, int ACTX, int RES>
+static int launch_tile(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p) {
+    constexpr bool bf_in = sizeof(TIN) == 2, bf_out = sizeof(TOUT) == 2;
+    constexpr bool n3 = (ACTX & 7) == 5, fold = (ACTX & (8 | 16)) != 0;
+    constexpr bool built = (!(fold || n3) || bf_in) && (!((ACTX & 4) || ACTX == 9 || ACTX == 16) || bf_out) && (ACTX != 48 || !bf_out);
+#define M324_TILE(KERNEL, T, TILE_N)                                                                                         \
+    hipLaunchKernelGGL(KERNEL, grid, block, 0, s, (const T*)a->A, a->lda, (const T*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, \
+                       a->N, a->K, ep, ceil_div(a->N, TILE_N), xcd_mode(a))
+    if constexpr (built) {
+        const dim3 grid((unsigned)p.wg, (unsigned)p.grid_y), block((unsigned)p.threads);
+        switch (p.variant) {
+            case 2:
+                if constexpr (!n3) { M324_TILE((gemm_glds_kernel<TIN, TOUT, ACTX, RES>), TIN, BN); return M324_OK; }
+                break;
+            case 5:
+                if constexpr (!n3 && !fold) { M324_TILE((gemm_glds5_kernel<TIN, TOUT, ACTX, RES>), TIN, BN5); return M324_OK; }
+                break;
+            case 10:
+                if constexpr (bf_in) { M324_TILE((gemm_ring_kernel<TOUT, ACTX, RES>), bf16_t, BN5); return M324_OK; }
+                break;
+            case 11:
+            case 12:
+                if constexpr (bf_in && !n3) return m324::launch_ring4(a, s, ep, p, xcd_mode(a));
+                break;
+            case 13:
+                if constexpr (bf_in && !n3) { M324_TILE((gemm_ring2_kernel<TOUT, ACTX, RES>), bf16_t, BN); return M324_OK; }
+                break;
+            default: break;
+        }
+    }
+#undef M324_TILE
+    M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: schedule %d does not build epilogue act=%d res=%d for dtypes in=%d out=%d", p.variant, ACTX, RES,
+              a->in_dtype, a->out_dtype);
+}
+
 template <typename TIN, typename TOUT>
 int launch(const m324_gemm_args* a, hipStream_t s) {
     const Epilogue ep = make_epilogue(a);
-    dim3 grid(ceil_div(a->N, BN), ceil_div(a->M, BM));
-    const int nbatch = a->batch > 1 ? a->batch : 1;
-    const bool lnf = a->ln_rowstat || a->ln_stats_out || a->ln_copy_out;     // LayerNorm fold: the ACT | 8 instantiations
-    if (a->aux_mode == M324_AUX_N3) {              // one schedule only: the 256 x 256 chunk ring (host-checked shape)
-        if constexpr (sizeof(TOUT) == 2 && sizeof(TIN) == 2) {
-            if (lnf)
-                hipLaunchKernelGGL((gemm_ring_kernel<bf16_t, 13, 0>), dim3(ring_grid(ceil_div(a->N, BN5) * ceil_div(a->M, BM5))), dim3(512), 0, s,
-                                   (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (bf16_t*)a->C, a->ldc, a->M, a->N, a->K, ep,
-                                   ceil_div(a->N, BN5), xcd_mode(a));
-            else
-                hipLaunchKernelGGL((gemm_ring_kernel<bf16_t, 5, 0>), dim3(ring_grid(ceil_div(a->N, BN5) * ceil_div(a->M, BM5))), dim3(512), 0, s,
-                                   (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (bf16_t*)a->C, a->ldc, a->M, a->N, a->K, ep,
-                                   ceil_div(a->N, BN5), xcd_mode(a));
-            M324_CHECK_LAUNCH("m324_gemm");
-            return M324_OK;
-        } else {
-            M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: M324_AUX_N3 is a bf16 mode");
-        }
-    }
-    const int variant = nbatch > 1 ? 2 : pick_variant(a);
-    if (variant == 15) {
-        const int rc_ = m324::launch_hp(a, s, ep, hp_act(a), hp_res(a), xcd_mode(a));
-        if (rc_ != M324_OK) return rc_;
-    } else if (variant == 1) {
-        hipLaunchKernelGGL((gemm_kernel<TIN, TOUT>), grid, dim3(256), 0, s, (const TIN*)a->A, a->lda, (const TIN*)a->W,
+    const GemmPlan p = make_plan(a);
+    const dim3 grid((unsigned)p.wg, (unsigned)p.grid_y), block((unsigned)p.threads);
+    int rc = M324_OK;
+    if (p.variant == 15) {
+        rc = m324::launch_hp(a, s, ep, p, xcd_mode(a));
+    } else if (p.variant == 1) {
+        hipLaunchKernelGGL((gemm_kernel<TIN, TOUT>), grid, block, 0, s, (const TIN*)a->A, a->lda, (const TIN*)a->W,
                            a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep);
-    } else if (variant == 9) {
-        if (a->act == M324_ACT_GELU)
-            hipLaunchKernelGGL((gemm_skinny_kernel<TOUT, 1>), dim3(ceil_div(a->N, 32)), dim3(512), 0, s, (const bf16_t*)a->A,
+    } else if (p.variant == 9) {
+        if (p.actx)
+            hipLaunchKernelGGL((gemm_skinny_kernel<TOUT, 1>), grid, block, 0, s, (const bf16_t*)a->A,
                                a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep);
         else
-            hipLaunchKernelGGL((gemm_skinny_kernel<TOUT, 0>), dim3(ceil_div(a->N, 32)), dim3(512), 0, s, (const bf16_t*)a->A,
+            hipLaunchKernelGGL((gemm_skinny_kernel<TOUT, 0>), grid, block, 0, s, (const bf16_t*)a->A,
                                a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep);
     } else {
-        const int res = !a->residual && a->row_gin <= 0 ? 0
-                        : (a->residual && a->row_gin <= 0 && (a->res_rows <= 0 || a->res_rows >= a->M)) ? 1 : 2;
-#define M324_GLDS(ACT, RES)                                                                                              \
-    do {                                                                                                                 \
-        if (variant >= 10) {                                                                             \
-            const int rc_ = launch_pipe<TOUT, ACT, RES>(a, s, ep, variant);                                              \
-            if (rc_ != M324_OK) return rc_;                                                                              \
-        }                                                                                                                \
-        else if (variant == 5)                                                                                           \
-            hipLaunchKernelGGL((gemm_glds5_kernel<TIN, TOUT, ACT, RES>),                                                 \
-                               dim3(ceil_div(a->N, BN5) * ceil_div(a->M, BM5)), dim3(512), 0, s, (const TIN*)a->A,       \
-                               a->lda, (const TIN*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N, a->K, ep,              \
-                               ceil_div(a->N, BN5), xcd_mode(a));                                                        \
-        else                                                                                                             \
-            hipLaunchKernelGGL((gemm_glds_kernel<TIN, TOUT, ACT, RES>), dim3(grid.x * grid.y, nbatch), dim3(256), 0, s,  \
-                               (const TIN*)a->A, a->lda, (const TIN*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, a->N,      \
-                               a->K, ep, (int)grid.x, xcd_mode(a));                                                      \
-    } while (0)
-        // LayerNorm fold: bf16 operands on the chunk-ring / 128 x 128 LDS-DMA kernels only (m324_gemm checked the shape)
-#define M324_LNF(ACT, RES)                                                                                               \
-    do {                                                                                                                 \
-        if (variant == 11 || variant == 12) {                                                                            \
-            const int rc_ = m324::launch_ring4(a, s, ep, ACT, RES, xcd_mode(a), variant);                                \
-            if (rc_ != M324_OK) return rc_;                                                                              \
-        } else if (variant == 13)                                                                                        \
-            hipLaunchKernelGGL((gemm_ring2_kernel<TOUT, ACT, RES>), dim3(grid.x * grid.y), dim3(256), 0, s,              \
-                               (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M,      \
-                               a->N, a->K, ep, (int)grid.x, xcd_mode(a));                                                \
-        else if (variant == 10)                                                                                          \
-            hipLaunchKernelGGL((gemm_ring_kernel<TOUT, ACT, RES>), dim3(ring_grid(ceil_div(a->N, BN5) * ceil_div(a->M, BM5))),      \
-                               dim3(512), 0, s, (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C,   \
-                               a->ldc, a->M, a->N, a->K, ep, ceil_div(a->N, BN5), xcd_mode(a));                          \
-        else                                                                                                             \
-            hipLaunchKernelGGL((gemm_glds_kernel<bf16_t, TOUT, ACT, RES>), dim3(grid.x * grid.y, 1), dim3(256), 0, s,    \
-                               (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M,      \
-                               a->N, a->K, ep, (int)grid.x, xcd_mode(a));                                                \
-    } while (0)
-        if (lnf) {                             // m324_gemm validated the combination: consumer XOR producer
-            if constexpr (sizeof(TIN) == 2) {
-                if (a->ln_rowstat) {               // consumer: ACT | 8, no residual
-                    if (a->aux_mode == M324_AUX_QKV_HEADS || a->aux_mode == M324_AUX_QKV_HEADS_VT) {
-                        if constexpr (sizeof(TOUT) == 2) M324_LNF(12, 0);
-                    } else if (a->act == M324_ACT_GELU) {
-                        if constexpr (sizeof(TOUT) == 2) M324_LNF(9, 0);
-                    } else {
-                        M324_LNF(8, 0);
-                    }
-                } else if constexpr (sizeof(TOUT) == 2) {      // producer, bf16 stream: statistics only
-                    if (res == 1) M324_LNF(16, 1); else M324_LNF(16, 2);
-                } else {                                        // producer, fp32 stream: statistics + bf16 twin
-                    if (res == 1) M324_LNF(48, 1); else M324_LNF(48, 2);
-                }
-            }
-        } else if (a->aux_mode == M324_AUX_QKV_HEADS || a->aux_mode == M324_AUX_QKV_HEADS_VT) {
-            if constexpr (sizeof(TOUT) == 2) M324_GLDS(4, 0);
-        } else if (a->aux_mode == M324_AUX_STORE_PREACT || a->aux_mode == M324_AUX_STORE_GELU_GRAD) {
-            M324_GLDS(2, 0);
-        } else if (a->aux_mode == M324_AUX_MUL_GELU_GRAD || a->aux_mode == M324_AUX_MUL) {
-            M324_GLDS(3, 0);
-        } else if (a->act == M324_ACT_GELU) {
-            if (res == 0) M324_GLDS(1, 0); else M324_GLDS(1, 2);
-        } else {
-            if (res == 0) M324_GLDS(0, 0); else if (res == 1) M324_GLDS(0, 1); else M324_GLDS(0, 2);
+        // every (ACTX, RES) make_plan derives; launch_tile says which of them a schedule and a dtype pair build
+#define M324_CODE(ACTX, RES) \
+    case (ACTX) * 4 + (RES): rc = launch_tile<TIN, TOUT, ACTX, RES>(a, s, ep, p); break
+        switch (p.actx * 4 + p.res) {
+            M324_CODE(0, 0); M324_CODE(0, 1); M324_CODE(0, 2); M324_CODE(1, 0); M324_CODE(1, 2); M324_CODE(2, 0); M324_CODE(3, 0);
+            M324_CODE(4, 0); M324_CODE(5, 0);
+            M324_CODE(8, 0); M324_CODE(9, 0); M324_CODE(12, 0); M324_CODE(13, 0);          // behind a folded LayerNorm
+            M324_CODE(16, 1); M324_CODE(16, 2); M324_CODE(48, 1); M324_CODE(48, 2);        // producers of its statistics
+            default: M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: no kernel for epilogue act=%d res=%d", p.actx, p.res);
         }
-#undef M324_GLDS
-#undef M324_LNF
+#undef M324_CODE
     }
+    if (rc != M324_OK) return rc;
     M324_CHECK_LAUNCH("m324_gemm");
     return M324_OK;
 }
@@ -1275,53 +1258,21 @@ int launch(const m324_gemm_args* a, hipStream_t s) {
 }  // namespace
 
 
-// Name (as rocprofv3's kernel trace prints the template, element types abbreviated) and grid in threads of the kernel
+// Name (as rocprofv3's kernel trace prints the template, element types abbreviated) and grid in threads (x, y, z) of the kernel
 // m324_gemm would launch for `a`: lets bench.py label its HIP-event rows with the same symbols the committed rocprof
-// summaries use.  Host-only; mirrors launch() above.
+// summaries use.  Host-only: formats make_plan(), the plan m324_gemm launches from.  Returns the schedule number.
 extern "C" int m324_gemm_plan(const m324_gemm_args* a, char* buf, int n) {
     M324_REQUIRE(a && buf && n > 0, "m324_gemm_plan: bad arguments");
-    const int nbatch = a->batch > 1 ? a->batch : 1;
-    const bool lnf = a->ln_rowstat || a->ln_stats_out || a->ln_copy_out;
-    if (a->aux_mode == M324_AUX_N3) {
-        snprintf(buf, (size_t)n, "gemm_ring_kernel<unsigned short, %d, 0> grid=%ldx1x1", lnf ? 13 : 5,
-                 (long)ring_grid((long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5)) * 512);
-        return 10;
-    }
-    const int variant = nbatch > 1 ? 2 : pick_variant(a);
+    const GemmPlan p = make_plan(a);
     const char* tout = a->out_dtype == M324_BF16 ? "unsigned short" : "float";
     const char* tin = a->in_dtype == M324_BF16 ? "unsigned short" : "float";
-    const int res = !a->residual && a->row_gin <= 0 ? 0
-                    : (a->residual && a->row_gin <= 0 && (a->res_rows <= 0 || a->res_rows >= a->M)) ? 1 : 2;
-    int act = a->act == M324_ACT_GELU ? 1 : 0, rs = act ? (res ? 2 : 0) : res;
-    if (a->aux_mode == M324_AUX_QKV_HEADS || a->aux_mode == M324_AUX_QKV_HEADS_VT) act = 4, rs = 0;
-    else if (a->aux_mode == M324_AUX_STORE_PREACT || a->aux_mode == M324_AUX_STORE_GELU_GRAD) act = 2, rs = 0;
-    else if (a->aux_mode == M324_AUX_MUL_GELU_GRAD || a->aux_mode == M324_AUX_MUL) act = 3, rs = 0;
-    if (lnf) {
-        if (a->ln_rowstat) act |= 8, rs = 0;
-        else act = a->out_dtype == M324_F32 ? 48 : 16, rs = res;
-    }
-    long wg = 0, threads = 256;
-    const char* name = "gemm_kernel";
-    switch (variant) {
-        case 1: wg = (long)ceil_div(a->N, BN) * ceil_div(a->M, BM); break;
-        case 2: name = "gemm_glds_kernel"; wg = (long)ceil_div(a->N, BN) * ceil_div(a->M, BM); break;
-        case 5: name = "gemm_glds5_kernel"; wg = (long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5); threads = 512; break;
-        case 9: name = "gemm_skinny_kernel"; wg = ceil_div(a->N, 32); threads = 512; break;
-        case 10: name = "gemm_ring_kernel"; wg = ring_grid((long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5)); threads = 512; break;
-        case 11: name = "gemm_ring4_kernel"; wg = (long)ceil_div(a->N, BN5) * ceil_div(a->M, BM5); if (wg > 256) wg = 256; break;
-        case 12: name = "gemm_ring3_kernel"; wg = (long)ceil_div(a->N, 128) * ceil_div(a->M, BM5); break;
-        case 13: name = "gemm_ring2_kernel"; wg = (long)ceil_div(a->N, BN) * ceil_div(a->M, BM); break;
-        case 15: name = "gemm_hp_kernel"; wg = m324::hp_grid(a); break;
-        default: break;
-    }
-    // grid in threads, as rocprofv3's kernel trace prints it (x, y, z)
-    if (variant == 1)
-        snprintf(buf, (size_t)n, "%s<%s, %s> grid=%dx%dx1", name, tin, tout, ceil_div(a->N, BN) * 256, ceil_div(a->M, BM));
-    else if (variant == 9) snprintf(buf, (size_t)n, "%s<%s, %d> grid=%ldx1x1", name, tout, act ? 1 : 0, wg * threads);
-    else if (variant == 2) snprintf(buf, (size_t)n, "%s<%s, %s, %d, %d> grid=%ldx%dx1", name, tin, tout, act, rs, wg * threads, nbatch);
-    else if (variant == 5) snprintf(buf, (size_t)n, "%s<%s, %s, %d, %d> grid=%ldx1x1", name, tin, tout, act, rs, wg * threads);
-    else snprintf(buf, (size_t)n, "%s<%s, %d, %d> grid=%ldx1x1", name, tout, act, rs, wg * threads);
-    return variant;
+    char targs[64];
+    if (p.variant == 1) snprintf(targs, sizeof(targs), "%s, %s", tin, tout);
+    else if (p.variant == 9) snprintf(targs, sizeof(targs), "%s, %d", tout, p.actx);
+    else if (p.variant == 2 || p.variant == 5) snprintf(targs, sizeof(targs), "%s, %s, %d, %d", tin, tout, p.actx, p.res);
+    else snprintf(targs, sizeof(targs), "%s, %d, %d", tout, p.actx, p.res);
+    snprintf(buf, (size_t)n, "%s<%s> grid=%ldx%dx1", p.name, targs, p.wg * p.threads, p.grid_y);
+    return p.variant;
 }
 
 extern "C" int m324_gemm_tn(const void* X, long ldx, const void* Y, long ldy, float* C, long ldc, int M, int N, int Kc,
@@ -1466,17 +1417,15 @@ extern "C" int m324_gemm_pair(const m324_gemm_args* a, const m324_gemm_args* b, 
     if (rc != M324_OK) return rc;
     rc = gemm_validate(b);
     if (rc != M324_OK) return rc;
-    auto heads = [](const m324_gemm_args* g) {
-        return (g->aux_mode == M324_AUX_QKV_HEADS || g->aux_mode == M324_AUX_QKV_HEADS_VT) && g->in_dtype == M324_BF16 && g->out_dtype == M324_BF16 &&
-               !g->residual && !g->ln_rowstat && !g->ln_stats_out && !g->ln_copy_out && g->batch <= 1 && g->act == M324_ACT_NONE;
-    };
-    if (!heads(a) || !heads(b) || pick_variant(a) != 13 || pick_variant(b) != 13)
+    // head-major q|k|v epilogue without a folded LayerNorm (ACTX 4) on the 128 x 128 chunk ring
+    const GemmPlan pa = make_plan(a), pb = make_plan(b);
+    if (pa.variant != 13 || pa.actx != 4 || pb.variant != 13 || pb.actx != 4)
         M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm_pair: built for two bf16 head-major projections on the 128 x 128 chunk ring");
-    auto problem = [](const m324_gemm_args* g) {
+    auto problem = [](const m324_gemm_args* g, const GemmPlan& p) {
         return Ring2Problem{(const bf16_t*)g->A, g->lda, (const bf16_t*)g->W, g->ldw, g->C, g->ldc, g->M, g->N, g->K, make_epilogue(g),
-                            ceil_div(g->N, BN), xcd_mode(g), ceil_div(g->N, BN) * ceil_div(g->M, BM)};
+                            ceil_div(g->N, BN), xcd_mode(g), (int)p.wg};
     };
-    const Ring2Problem p0 = problem(a), p1 = problem(b);
+    const Ring2Problem p0 = problem(a, pa), p1 = problem(b, pb);
     hipLaunchKernelGGL((gemm_ring2_pair_kernel<bf16_t, 4, 0>), dim3(p0.tiles + p1.tiles), dim3(256), 0, (hipStream_t)stream, p0, p1);
     M324_CHECK_LAUNCH("m324_gemm_pair");
     return M324_OK;

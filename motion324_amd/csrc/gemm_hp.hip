@@ -78,42 +78,31 @@ constexpr int HP_MAX_TILES = HP_TABLE_BYTES / 48 - 2;
 #undef HP_ASM_INC
 #undef HP_ST_FLAG
 
-int hp_cus() {
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n - (n & 7);                                  // a multiple of 8: tile t and t + grid share an XCD
-    }();
-    return n_cu;
-}
-
 }  // namespace
 
 namespace m324 {
 
 // what the stream handles; the chooser (gemm.hip pick_variant) asks before it sends a GEMM here
-bool hp_ok(const m324_gemm_args* a, const Epilogue& ep, int act_code, int res_code) {
-    if (a->K != 768 || a->N % 128 != 0 || a->M < 1 || a->out_dtype != M324_BF16 || res_code != 0) return false;
-    if (act_code < 0) return false;
-    if (act_code != 0 && act_code != 1 && act_code != 8 && act_code != 9) return false;
-    if (ep.gamma || ep.aux || ep.stats || ep.copy || ep.row_gin > 0) return false;
-    if ((act_code & 8) && (!ep.rowstat || !ep.colsum || ep.ncb > 0)) return false;
+bool hp_ok(const m324_gemm_args* a, const Epilogue& ep, int actx, int max_wg) {
+    if (a->K != 768 || a->N % 128 != 0 || a->M < 1 || a->out_dtype != M324_BF16) return false;
+    if (actx != 0 && actx != 1 && actx != 8 && actx != 9) return false;      // bias (+ GELU), and both behind a folded LayerNorm
+    if (ep.residual || ep.gamma || ep.aux || ep.stats || ep.copy || ep.row_gin > 0) return false;
+    if ((actx & 8) && (!ep.rowstat || !ep.colsum || ep.ncb > 0)) return false;
     if ((a->lda & 7) || (a->ldw & 7) || (a->ldc & 7) || ((uintptr_t)a->A & 15) || ((uintptr_t)a->W & 15) || ((uintptr_t)a->C & 15) || ((uintptr_t)ep.bias & 15) ||
         ((uintptr_t)ep.colsum & 15))
         return false;
     if ((long)a->M * a->lda * 2 >= 0x7fffffffl || 256l * a->ldc * 2 >= 0x7fffffffl || (long)a->N * a->ldw * 2 >= 0x7fffffffl) return false;
-    const int ntiles = (a->N / 128) * ceil_div(a->M, 256), grid = ntiles < hp_cus() ? ntiles : hp_cus();
+    const int ntiles = (a->N / 128) * ceil_div(a->M, 256), grid = ntiles < max_wg ? ntiles : max_wg;
     return ceil_div(ntiles, grid) <= HP_MAX_TILES;
 }
 
-int launch_hp(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int act_code, int res_code, int xcd_remap) {
-    if (!hp_ok(a, ep, act_code, res_code)) M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: schedule v15 does not take this GEMM (K = 768, bf16, bias, act=%d res=%d)", act_code, res_code);
+int launch_hp(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p, int xcd_remap) {
     const int ntn = a->N / 128, ntiles = ntn * ceil_div(a->M, 256);
-    const dim3 grid(ntiles < hp_cus() ? ntiles : hp_cus());
+    const dim3 grid((unsigned)p.wg);
 #define M324_HP(KERNEL)                                                                                                              \
     hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, (const bf16_t*)a->A, a->lda, (const bf16_t*)a->W, a->ldw, (bf16_t*)a->C, a->ldc, a->M, a->N, \
                        ep.bias, ep.colsum, ep.rowstat, ntn, ntiles, xcd_remap)
-    switch (act_code + (ep.stream ? 16 : 0)) {
+    switch (p.actx + (ep.stream ? 16 : 0)) {
         case 0: M324_HP(gemm_hp_plain_kernel); break;
         case 1: M324_HP(gemm_hp_gelu_kernel); break;
         case 8: M324_HP(gemm_hp_fold_kernel); break;
@@ -121,15 +110,11 @@ int launch_hp(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int ac
         case 16: M324_HP(gemm_hp_plain_nt_kernel); break;
         case 17: M324_HP(gemm_hp_gelu_nt_kernel); break;
         case 24: M324_HP(gemm_hp_fold_nt_kernel); break;
-        default: M324_HP(gemm_hp_fold_gelu_nt_kernel); break;
+        case 25: M324_HP(gemm_hp_fold_gelu_nt_kernel); break;
+        default: M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: schedule v15 has no stream for epilogue act=%d", p.actx);
     }
 #undef M324_HP
     return M324_OK;
-}
-
-int hp_grid(const m324_gemm_args* a) {
-    const int ntiles = (a->N / 128) * ceil_div(a->M, 256);
-    return ntiles < hp_cus() ? ntiles : hp_cus();
 }
 
 }  // namespace m324

@@ -322,15 +322,10 @@ __global__ __launch_bounds__(256) void gemm_ring3_kernel(const bf16_t* __restric
 
 namespace m324 {
 
-int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int act_code, int res_code, int xcd_remap, int variant) {
+int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p, int xcd_remap) {
+    const int variant = p.variant;
     const int ntn = ceil_div(a->N, variant == 12 ? 128 : BN5), ntiles = ntn * ceil_div(a->M, BM5);
-    static const int n_cu = [] {                            // v11: one persistent workgroup per CU (160 KiB of LDS each)
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
-    const dim3 grid(variant == 12 ? ntiles : (ntiles < n_cu ? ntiles : n_cu));
+    const dim3 grid((unsigned)p.wg);                         // v11: one persistent workgroup per CU (160 KiB of LDS each); v12: one per tile
 #define M324_R4(TOUT, ACT, RES)                                                                                              \
     do {                                                                                                                     \
         if (variant == 12)                                                                                            \
@@ -346,8 +341,7 @@ int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int
         if (a->out_dtype == M324_BF16) M324_R4(bf16_t, ACT, RES);  \
         else M324_R4(float, ACT, RES);                             \
     } while (0)
-    const int key = act_code * 4 + res_code;
-    switch (key) {
+    switch (p.actx * 4 + p.res) {
         case 0 * 4 + 0: M324_R4_OUT(0, 0); break;
         case 0 * 4 + 1: M324_R4_OUT(0, 1); break;
         case 0 * 4 + 2: M324_R4_OUT(0, 2); break;
@@ -364,7 +358,7 @@ int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int
         case 48 * 4 + 1: M324_R4(float, 48, 1); break;     // ... and of an fp32 stream (statistics + bf16 twin)
         case 48 * 4 + 2: M324_R4(float, 48, 2); break;
         default:                   // m324_gemm only builds the combinations above
-            M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: no 4-wave ring kernel for epilogue act=%d res=%d", act_code, res_code);
+            M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: no 4-wave ring kernel for epilogue act=%d res=%d", p.actx, p.res);
     }
 #undef M324_R4_OUT
 #undef M324_R4

@@ -39,13 +39,24 @@ struct Epilogue {
     float eps;                   // ... with this LayerNorm epsilon (what m324_rowstats_finish does in a launch of its own)
 };
 
-// gemm_ring4.hip (own translation unit: built WITHOUT -amdgpu-mfma-vgpr-form, its 256 accumulators live in AGPRs).
-// act_code: the ACT template value (0 none, 1 GELU, 2 GELU + pre-activation, 3 x gelu', 4 q|k|v heads); res_code: RES.
-int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int act_code, int res_code, int xcd_remap, int variant);
+// What one m324_gemm call launches.  gemm.hip make_plan() is the only place that fills it; the launchers and the m324_gemm_plan
+// query read it.
+struct GemmPlan {
+    int variant;                 // schedule number (1, 2, 5, 9, 10, 11, 12, 13, 15)
+    int actx, res;               // the kernel's ACTX / RES template codes (ACTX bits: store_tile_lds below)
+    int nbatch;                  // problems in the launch (schedule 2 only)
+    const char* name;            // the kernel's base name
+    long wg;                     // workgroups along x
+    int threads;                 // per workgroup
+    int grid_y;                  // schedule 1: row tiles; schedule 2: nbatch; otherwise 1
+};
+
+// gemm_ring4.hip (own translation unit: built WITHOUT -amdgpu-mfma-vgpr-form, its 256 accumulators live in AGPRs): schedules 11, 12
+int launch_ring4(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p, int xcd_remap);
 // gemm_hp.hip (v15: the hand-placed K = 768 stream, previous tile's epilogue inside the main loop); hp_ok: does it take this GEMM
-bool hp_ok(const m324_gemm_args* a, const Epilogue& ep, int act_code, int res_code);
-int launch_hp(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, int act_code, int res_code, int xcd_remap);
-int hp_grid(const m324_gemm_args* a);
+// (actx as make_plan() derives it) on a grid of at most max_wg workgroups
+bool hp_ok(const m324_gemm_args* a, const Epilogue& ep, int actx, int max_wg);
+int launch_hp(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p, int xcd_remap);
 }  // namespace m324
 
 namespace {
@@ -55,6 +66,7 @@ constexpr int BM = 128, BN = 128, ROWB = 128;           // ROWB: bytes of K per 
 constexpr int TILE_BYTES = BM * ROWB;                   // 16 KiB per operand per stage
 
 using m324::Epilogue;
+using m324::GemmPlan;
 
 // GELU for the bf16 path: erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7 absolute, far below the
 // bf16 rounding of the result); the fp32 parity path keeps erff.  ~12 VALU + 2 transcendental ops

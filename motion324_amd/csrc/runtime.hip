@@ -38,6 +38,17 @@ struct TunInit {
 
 int m324::tunable(int which) { return g_tun[which].load(std::memory_order_relaxed); }
 
+// the persistent GEMM schedules size their grids by it (v10 / v15 round down to a multiple of 8, v11 takes it as it is)
+int m324::cu_count() {
+    static const int n_cu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return n_cu;
+}
+
 extern "C" int m324_set_tunable(const char* name, int value) {
     M324_REQUIRE(name, "m324_set_tunable: null name");
     for (int i = 0; i < m324::TUN_COUNT; ++i)

@@ -67,10 +67,15 @@ def _rows(t: torch.Tensor, name: str):
     return _p(t), t.stride(0)
 
 
-def _gemm_plan(args) -> str:
+def _gemm_query(args):
+    """(schedule number, kernel name and grid) of the launch m324_gemm would make for `args`: m324_gemm_plan, host-only"""
     buf = C.create_string_buffer(192)
-    L.load().m324_gemm_plan(C.byref(args), buf, 192)
-    return buf.value.decode()
+    schedule = int(L.load().m324_gemm_plan(C.byref(args), buf, 192))
+    return schedule, buf.value.decode()
+
+
+def _gemm_plan(args) -> str:
+    return _gemm_query(args)[1]
 
 
 def gemm_schedule(M: int, N: int, K: int, *, act: int = L.ACT_NONE, out_dtype: torch.dtype = torch.bfloat16, bias: bool = True,
@@ -86,8 +91,7 @@ def gemm_schedule(M: int, N: int, K: int, *, act: int = L.ACT_NONE, out_dtype: t
         args.bias = 4096
     if fold_merged:
         args.ln_rowstat, args.ln_colsum, args.ln_ncb, args.ln_eps = 4096, 4096, 0, 1e-5
-    buf = C.create_string_buffer(192)
-    return int(L.load().m324_gemm_plan(C.byref(args), buf, 192))
+    return _gemm_query(args)[0]
 
 
 def _attn_plan(B, H, Lq, Lk, flags, dtype_code) -> str:
@@ -565,12 +569,12 @@ def attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, out: torch.Ten
     qbs = 0 if shared_q else H * Lq * 64
     scale = 64 ** -0.5 if scale is None else scale
     esz = Q.element_size()
+    flags = int(prescaled) | (2 if v_rowmajor else 0) | (4 if bounded else 0)       # M324_ATTN_*; the plan query takes shared_q as bit 8
     with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * Lq * Lk * 64,
               esz * 64.0 * H * ((1 if shared_q else B) * Lq + 2 * B * Lk + B * Lq),
-              f"{_attn_plan(B, H, Lq, Lk, int(prescaled) | (2 if v_rowmajor else 0) | (4 if bounded else 0) | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk}"
+              f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk}"
               if _timing() else ""):
-        L.check(L.load().m324_attention(_p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale,
-                                        int(prescaled) | (2 if v_rowmajor else 0) | (4 if bounded else 0), _p(lse), code_of(Q.dtype), _stream()),
+        L.check(L.load().m324_attention(_p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale, flags, _p(lse), code_of(Q.dtype), _stream()),
                 "m324_attention")
     return out
 

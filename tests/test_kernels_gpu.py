@@ -460,12 +460,17 @@ def test_gemm_skinny_rows(M, N, K):
     assert rel_err(x, res.double() + a.double() @ w.double().T) < 1e-5
 
 
+@pytest.mark.parametrize("variant", ["v0", "v2", "v5", "v10", "v11", "v12", "v13"])
 @pytest.mark.parametrize("dtype", DT)
 @pytest.mark.parametrize("M,N,K", [(300, 328, 192), (512, 768, 256), (40, 64, 64)])
-def test_gemm_training_aux_operand(dtype, M, N, K):
+def test_gemm_training_aux_operand(dtype, M, N, K, variant, tune):
     """M324_AUX_STORE_PREACT: one launch yields gelu(z) and z; M324_AUX_MUL_GELU_GRAD: result * gelu'(z)
-    (ragged tiles, interior 16-byte-store path at N % 64 == 0, and the small-M route around the skinny kernel)."""
+    (ragged tiles, interior 16-byte-store path at N % 64 == 0, and the small-M route around the skinny kernel).
+    On the chooser's schedule (v0) and on every forced tile / ring schedule: the ACTX 2 / 3 instantiations of each kernel, which only
+    the full-size training steps reach otherwise (fp32 operands and K = 64 fall back as the chooser maps them)."""
     ops = _ops()
+    if variant != "v0":
+        tune("M324_GEMM", variant)
     from motion324_amd.lib import ACT_GELU, M324Error
     a, w = _q(_rand((M, K), 31), dtype), _q(_rand((N, K), 32, 0.1), dtype)
     bias = _rand((N,), 33)
