@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import ops, parallel, switches
 from .easydict import EasyDict as edict
 from .image_encoder import DINO_EPS, DinoEncoder
+from .latent import MotionLatent
 from .lib import ACT_GELU, M324Error
 from .loss import MSELossComputer
 from .prepared import Prepared, bump_generation, compute_dtype, pad_k
@@ -41,8 +42,33 @@ KV_REHEARSE = int(switches.get("M324_KV_REHEARSE") or 0)       # one-rank rehear
 KV_OVERLAP = switches.flag("M324_KV_OVERLAP")              # frame-parallel: own keys attended while the K|V all-gather is in flight
 BF16_DECODER_STREAM = switches.flag("M324_BF16_DECODER")    # the decoder's residual stream in bf16 (bf16 inference only)
 HOIST_DECODER_Q = switches.flag("M324_HOIST_Q")             # hoisted decoder q projection (graph capture)
+_PATH_ROWS = 64           # at most this many rows: the bf16 kernels' small-problem paths (decode-only chunk plans stay off the line)
 DECODE_ROWS = int(switches.get("M324_DECODE_ROWS"))         # max (frames x points) rows per decoder pass: bounds the [rows, 4C] MLP buffer
 MXFP8_DEFAULT = switches.flag("M324_MXFP8")                # inference_precision of a model whose config names none: "mxfp8" (1) / "bf16"
+
+
+def decode_plan(N: int, T: int, rows: int):
+    """(points per pass, frames per pass) of a decode-only call over N points and T frames under a budget of `rows`
+    (frame, point) rows per pass.  Frames are cut in even chunks (attn_frames_kernel works on frame pairs).  The bf16 kernels change
+    path at 64 rows (transformer.fuse_proj, LNFold.usable, the skinny GEMM): every pass stays on the whole decode's side of that
+    line, in its points (point features, q projection) and in its (frame, point) rows, so that the plan cannot change a bit of
+    the result -- even where a budget below 130 rows asked for less."""
+    nchunk, tchunk = max(1, min(N, rows // T)), T
+    if N * T <= rows:
+        return nchunk, tchunk
+    if 2 * N <= rows:                          # few points, many frames: all points in every pass, as many frame pairs as fit
+        nchunk, tchunk = N, (rows // N) & ~1
+    elif (_PATH_ROWS + 1) * T > rows:          # many of both: passes of more than 64 points would not hold all frames
+        tchunk = min(T, max(2, (rows // (_PATH_ROWS + 1)) & ~1))
+        nchunk = max(1, min(N, rows // tchunk))
+    if N > _PATH_ROWS:
+        nchunk = max(nchunk, _PATH_ROWS + 1)
+    while tchunk * nchunk <= _PATH_ROWS < T * N:
+        if nchunk < N:
+            nchunk = min(N, _PATH_ROWS // tchunk + 1)
+        else:
+            tchunk = min(T, tchunk + 2)
+    return nchunk, tchunk
 
 
 def _get(cfg, key, default=None):
@@ -466,7 +492,11 @@ class Motion_Latent_Model(nn.Module):
             return None
         finally:
             self.__dict__["_ag_busy"] = False
-        out = edict(input_data=sample, pcd_moved=res.pcd_moved.clone())
+        out = edict(input_data=sample)
+        if "pcd_moved" in res:                              # (an encode-only call returns no trajectories)
+            out.pcd_moved = res.pcd_moved.clone()
+        if "latent" in res:
+            out.latent = res.latent.clone()
         if "reuse" in res:
             out.reuse = edict({k: v.clone() for k, v in res.reuse.items()})
         if "loss_metrics" in res:
@@ -522,8 +552,190 @@ class Motion_Latent_Model(nn.Module):
             raise M324Error("forward_frame_parallel(local_frames=True) needs total_frames")
         return self._forward(sample, (rank, world, group, int(total_frames) if local_frames else None))
 
-    def _forward(self, sample: Dict[str, torch.Tensor], shard):
+    # ------------------------------------------------------------------------------------ the motion latent
+    def _latent_guard(self, shard, both: bool) -> None:
+        if shard is not None:
+            raise M324Error("forward_frame_parallel: the motion latent keys (m324_latent / m324_keep_latent / m324_encode_only) "
+                            "are single-GPU only")
+        if self.training or torch.is_grad_enabled():
+            raise M324Error("the motion latent is an inference interface: call model.eval() and run under torch.no_grad()")
+        if both:
+            raise M324Error("m324_latent (decode only) excludes m324_keep_latent / m324_encode_only")
+
+    def _forward_decode(self, sample: Dict[str, torch.Tensor], latent_in: torch.Tensor):
+        """Stages E-F on a handed-in latent [B, T, K, C]: no clip, no shape samples."""
         ref_pcd = sample["ref_pcd"]
+        dev = ref_pcd.device
+        if dev.type != "cuda" or latent_in.device.type != "cuda":
+            raise M324Error("motion324_amd.Motion_Latent_Model runs only on a HIP device (model.to('cuda'), inputs on "
+                            "'cuda'); there is no CPU fallback on this path")
+        C, K = self.embed_dim, self.num_learnable_tokens
+        if latent_in.dim() != 4 or tuple(latent_in.shape[2:]) != (K, C) or latent_in.shape[1] < 1:
+            raise M324Error(f"m324_latent: expected [B, T, {K}, {C}], got {tuple(latent_in.shape)}")
+        B, T = latent_in.shape[0], latent_in.shape[1]
+        if ref_pcd.dim() != 3 or ref_pcd.shape[0] != B:
+            raise M324Error(f"m324_latent holds {B} sample(s), ref_pcd {tuple(ref_pcd.shape)}")
+        P = Prepared.for_module(self, dev, compute_dtype())
+        lat = self._f32c(latent_in).reshape(B * T * K, C)
+        out = self._decode(P, sample, lat, (0, 0, 0), B, T, None, getattr(self, "_capture", None), frame_chunks=True)
+        result = edict(input_data=sample, pcd_moved=out)
+        if "point_clouds" in sample:
+            m = self.loss_computer(out, sample["point_clouds"].to(dev))
+            lm = edict()
+            lm.loss = m.loss
+            lm.xyz_loss = m.coord_mse_loss
+            result.loss_metrics = lm
+        return result
+
+    def encode_motion(self, sample: Dict[str, torch.Tensor]) -> MotionLatent:
+        """Stages A-D only (shape encoder, image encoder, trunk): the clip's motion latent, 64 tokens per frame, from which
+        decode_motion moves any point set.  Reads what the forward reads on that side -- `rgb_video` (fp32 or uint8),
+        `ref_shape_pcd / _normals / _rgbs`, optionally `m324_mesh_tokens` / `m324_anchor_tokens` -- and no mesh points.  Precision
+        follows the caller like the forward's (autocast / set_precision / inference_precision).  The tokens are the caller's own
+        memory."""
+        self._latent_guard(None, False)
+        if "rgb_video" not in sample:
+            raise M324Error("encode_motion: the sample holds no rgb_video")
+        s = {k: v for k, v in sample.items() if k not in ("ref_pcd", "ref_normal", "ref_rgb", "point_clouds", "m324_latent",
+                                                          "m324_keep_reuse", "m324_keep_latent")}
+        s["m324_encode_only"] = True
+        out = self._forward_auto_graph(s)
+        if out is None:
+            out = self._forward(s, None)
+        return MotionLatent(out.latent, d=self.embed_dim, K=self.num_learnable_tokens, frames=self.video_length)
+
+    def decode_motion(self, latent: MotionLatent, ref_pcd, ref_normal, ref_rgb, frames=None) -> torch.Tensor:
+        """Stages E-F only: the mesh points [B, N, 3] (x3) moved by the latent's frames -> fp32 [B, T', N, 3].  frames: an
+        index list or a slice into the latent's frames (default: all, in order)."""
+        self._latent_guard(None, False)
+        if not isinstance(latent, MotionLatent):
+            raise M324Error(f"decode_motion: expected a MotionLatent, got {type(latent).__name__}")
+        if (latent.d, latent.K) != (self.embed_dim, self.num_learnable_tokens):
+            raise M324Error(f"decode_motion: the latent was encoded by a model with d = {latent.d}, {latent.K} tokens; this "
+                            f"model has d = {self.embed_dim}, {self.num_learnable_tokens} tokens")
+        tokens = latent.tokens
+        if any(t.device.type != "cuda" for t in (tokens, ref_pcd, ref_normal, ref_rgb)):
+            raise M324Error("decode_motion runs only on a HIP device (latent.to('cuda'), points on 'cuda'); there is no CPU "
+                            "fallback on this path")
+        if tokens.dim() != 4 or ref_pcd.dim() != 3 or tokens.shape[0] != ref_pcd.shape[0]:
+            raise M324Error(f"decode_motion: latent {tuple(tokens.shape)} and ref_pcd {tuple(ref_pcd.shape)} disagree on the batch")
+        n_out = None
+        if frames is not None:
+            T = tokens.shape[1]
+            idx = list(range(T))[frames] if isinstance(frames, slice) else [int(t) for t in frames]
+            if not idx or any(not (-T <= t < T) for t in idx):
+                raise M324Error(f"decode_motion: frames {frames!r} out of a latent of {T} frames")
+            sel = [t % T for t in idx]
+            # The bf16 kernels change path at 64 rows (transformer.fuse_proj, LNFold.usable, the skinny GEMM), and a frame must
+            # not depend on which other frames are asked for: a subset that would fall to the other side of that line than the
+            # whole latent -- in the decoder's (frame, point) rows or in the k|v side's (frame, token) rows -- is decoded with
+            # its last frame repeated, and the repeats are dropped.
+            n_out, B, N, K = len(sel), tokens.shape[0], ref_pcd.shape[1], tokens.shape[2]
+            while len(sel) * N <= _PATH_ROWS < T * N or B * len(sel) * K <= _PATH_ROWS < B * T * K:
+                sel.append(sel[-1])
+            tokens = tokens.index_select(1, torch.tensor(sel, dtype=torch.long).to(tokens.device))
+        s = {"m324_latent": tokens, "ref_pcd": ref_pcd, "ref_normal": ref_normal, "ref_rgb": ref_rgb}
+        out = self._forward_auto_graph(s)
+        if out is None:
+            out = self._forward(s, None)
+        out = out.pcd_moved
+        return out if n_out is None or n_out == out.shape[1] else out[:, :n_out].contiguous()
+
+    def _decode(self, P: Prepared, sample, tok: torch.Tensor, row_map, B: int, T: int, hoisted, cap, frame_chunks: bool = False):
+        """Stages E+F for one forward: tok fp32 rows that hold every frame's K latent tokens -- the trunk's stream with
+        row_map (K, Lt, 4), or a handed-in latent [B*T*K, C] with the identity map -- and the sample's mesh points -> fp32
+        [B, T, N, 3].  frame_chunks (decode-only calls: any number of frames, any number of points): a pass that would exceed
+        DECODE_ROWS is cut over frames as well, in even chunks (attn_frames_kernel works on frame pairs), with the queries of
+        a point chunk projected once for all of its frame chunks.  Such a plan is invisible in the result, bit for bit: every pass
+        stays on the whole decode's side of the 64-row line at which the bf16 kernels change path, and a last, shorter chunk is
+        moved back to full size over rows that are already written.  (The closed forward's plan is the parent's: point chunks
+        only, and in bf16 a last chunk of at most 64 rows runs the small-problem kernels.)"""
+        ref_pcd = sample["ref_pcd"]
+        dev = ref_pcd.device
+        N = ref_pcd.shape[1]
+        C, K = self.embed_dim, self.num_learnable_tokens
+        # E+F. decoder (reference :520-579): the mesh points are projected once per sample and attend to
+        # each frame's K latent tokens; rows = (frame, point).
+        dec = self.decoder_cross_attn
+        out = torch.empty((B, T, N, 3), dtype=torch.float32, device=dev)
+        head_ln, head_fc1, head_fc2 = self.shared_mlp_output[0], self.shared_mlp_output[1], self.shared_mlp_output[3]
+        w3, b3 = P.f32(head_fc2.weight), P.vec(head_fc2.bias)
+        # reference FLOPs of the decoder cross-attention block (SURVEY 8(d); to_q counted once per frame as the
+        # reference computes it) -- attached to the stage span bench.py reports the 40 % MFMA target on
+        nchunk, tchunk = decode_plan(N, T, DECODE_ROWS) if frame_chunks else (max(1, min(N, DECODE_ROWS // T)), T)
+        pcd, nrm, rgb = (self._f32c(sample[k]) for k in ("ref_pcd", "ref_normal", "ref_rgb"))
+        paired = None
+        if hoisted is None and B == 1 and nchunk == N and tchunk == T:
+            # one sample in one pass and the q projection inside the block: its LayerNorm / projection share their launches
+            # with the k|v side's (transformer.project_q_kv)
+            pf0 = self._point_features(P, pcd[0], nrm[0].contiguous(), rgb[0].contiguous())
+            with span("stage:decoder_cross_attn_block", self.decoder_block_flops(B, T, N)):
+                Q0, Kd, Vd = dec.project_q_kv(P, pf0, N, tok, B * T, K, row_map=row_map)
+            paired = (pf0, Q0)
+        else:
+            with span("stage:decoder_cross_attn_block", self.decoder_block_flops(B, T, N)):
+                Kd, Vd = dec.project_kv(P, tok, B * T, K, row_map=row_map)       # the forward: latent tokens 4..4+K of every frame
+        for b in range(B):
+            for n0 in range(0, N, nchunk):
+                if frame_chunks:                   # the last pass is moved back to full size (same rows, same values, written twice)
+                    n0 = min(n0, N - nchunk)
+                n1 = min(N, n0 + nchunk)
+                if hoisted is not None:
+                    pf, Q = hoisted[b]
+                elif paired is not None:
+                    pf, Q = paired
+                else:
+                    pf = self._point_features(P, pcd[b, n0:n1], nrm[b, n0:n1].contiguous(), rgb[b, n0:n1].contiguous())
+                if tchunk < T and hoisted is None and paired is None:
+                    with span("stage:decoder_cross_attn_block", 0.0):
+                        Q = dec.project_q(P, pf, 1, n1 - n0)
+                for t0 in range(0, T, tchunk):
+                    if frame_chunks:
+                        t0 = min(t0, T - tchunk)
+                    t1 = min(T, t0 + tchunk)
+                    with span("stage:decoder_cross_attn_block", 0.0):
+                        x, fold_d = self.decoder_block(P, Kd[b * T + t0:b * T + t1], Vd[b * T + t0:b * T + t1], pf,
+                                                       None if (hoisted is None and paired is None and tchunk == T) else Q)
+                    if cap is not None and n0 == 0 and n1 == N and tchunk == T:
+                        cap.setdefault("decoder_out_t0", []).append(x[:N].clone())
+                    if fold_d is not None:
+                        # the head's LayerNorm rides in its first GEMM: statistics left by the MLP's last epilogue
+                        hw, hcs, hb = P.folded(head_ln.weight, head_ln.bias, head_fc1.weight, head_fc1.bias)
+                        h, lnk = fold_d.xb, dict(ln=fold_d.ln(head_ln.eps, hcs))
+                    else:
+                        h = torch.empty(x.shape, dtype=P.dtype, device=dev)
+                        ops.layernorm(x, P.vec(head_ln.weight), P.vec(head_ln.bias), head_ln.eps, h)
+                        hw, hb, lnk = P.mat(head_fc1.weight), P.vec(head_fc1.bias), {}
+                    whole = n0 == 0 and n1 == N and tchunk == T
+                    o = out[b] if whole else torch.empty((t1 - t0, n1 - n0, 3), dtype=torch.float32, device=dev)
+                    if FUSE_HEAD_N3 and P.dtype == torch.bfloat16 and C % 256 == 0 and not torch.is_grad_enabled():
+                        # Linear -> GELU -> Linear(C -> 3) without the [rows, C] intermediate: the first GEMM's epilogue contracts
+                        # its GELU output with the 3 x C weight and leaves C / 64 partial sums per row (M324_AUX_N3)
+                        part = torch.empty((C // 64, x.shape[0], 3), dtype=torch.float32, device=dev)
+                        ops.gemm(h, hw, None, bias=hb, act=ACT_GELU, n3=(w3, part), **lnk)
+                        ops.n3_finish(part, b3, o)
+                    else:
+                        h2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
+                        ops.gemm(h, hw, h2, bias=hb, act=ACT_GELU, **lnk)
+                        ops.linear_n3(h2, w3, b3, o)
+                    if not whole:
+                        out[b, t0:t1, n0:n1] = o
+        if cap is not None and "decoder_out_t0" in cap:
+            cap["decoder_out_t0"] = torch.stack(cap["decoder_out_t0"], dim=0)
+        return out
+
+    def _forward(self, sample: Dict[str, torch.Tensor], shard):
+        # The motion latent as an interface (encode_motion / decode_motion): `m324_encode_only` ends the forward behind stage D,
+        # `m324_keep_latent` makes the result carry `latent` (fp32 [B, T, K, C]: rows 4..4+K of every frame of the trunk's
+        # stream), `m324_latent` hands such a latent in and runs stages E-F only.  None of them: the forward below, unchanged.
+        latent_in = sample.get("m324_latent")
+        encode_only = bool(sample.get("m324_encode_only", False))
+        keep_latent = bool(sample.get("m324_keep_latent", False)) or encode_only
+        if latent_in is not None or keep_latent:
+            self._latent_guard(shard, latent_in is not None and keep_latent)
+        if latent_in is not None:
+            return self._forward_decode(sample, latent_in)
+        ref_pcd = sample["rgb_video"] if encode_only else sample["ref_pcd"]      # encode-only: the clip says device and batch
         dev = ref_pcd.device
         if dev.type != "cuda":
             raise M324Error("motion324_amd.Motion_Latent_Model runs only on a HIP device (model.to('cuda'), inputs on "
@@ -531,7 +743,7 @@ class Motion_Latent_Model(nn.Module):
         P = Prepared.for_module(self, dev, compute_dtype())
         mx = mx_scope(_transformer.MX_ROLES if shard is None and self.mx_effective() else ())      # MXFP8: image encoder + trunk
         cap = getattr(self, "_capture", None)      # tests: dict that receives clones of stage activations
-        B, N, _ = ref_pcd.shape
+        B, N = ref_pcd.shape[0], (0 if encode_only else ref_pcd.shape[1])
         C, K = self.embed_dim, self.num_learnable_tokens
         S = sample["ref_shape_pcd"].shape[1]
 
@@ -569,7 +781,7 @@ class Motion_Latent_Model(nn.Module):
             # the decoder's point features and q projection depend on the mesh points only: under graph capture they
             # ride on this branch too (seven small launches, ~40 us, off the critical path between trunk and decoder)
             hoisted = None
-            if (HOIST_DECODER_Q and side is not None and torch.cuda.is_current_stream_capturing()
+            if (HOIST_DECODER_Q and side is not None and not encode_only and torch.cuda.is_current_stream_capturing()
                     and DECODE_ROWS // (sample["rgb_video"].shape[1] + (anchor_in is not None)) >= N):
                 pcd_h, nrm_h, rgb_h = (self._f32c(sample[k]) for k in ("ref_pcd", "ref_normal", "ref_rgb"))
                 hoisted = []
@@ -653,65 +865,15 @@ class Motion_Latent_Model(nn.Module):
         if cap is not None:
             cap["trunk_out"] = tok.clone()
 
-        # E+F. decoder (reference :520-579): the mesh points are projected once per sample and attend to
-        # each frame's K latent tokens; rows = (frame, point).
-        dec = self.decoder_cross_attn
-        out = torch.empty((B, T, N, 3), dtype=torch.float32, device=dev)
-        head_ln, head_fc1, head_fc2 = self.shared_mlp_output[0], self.shared_mlp_output[1], self.shared_mlp_output[3]
-        w3, b3 = P.f32(head_fc2.weight), P.vec(head_fc2.bias)
-        # reference FLOPs of the decoder cross-attention block (to_q counted once per frame as the
-        # reference computes it) -- attached to the stage span bench.py reports the 40 % MFMA target on
-        nchunk = max(1, min(N, DECODE_ROWS // T))
-        pcd, nrm, rgb = (self._f32c(sample[k]) for k in ("ref_pcd", "ref_normal", "ref_rgb"))
-        paired = None
-        if hoisted is None and B == 1 and nchunk == N:
-            # one sample in one pass and the q projection inside the block: its LayerNorm / projection share their launches
-            # with the k|v side's (transformer.project_q_kv)
-            pf0 = self._point_features(P, pcd[0], nrm[0].contiguous(), rgb[0].contiguous())
-            with span("stage:decoder_cross_attn_block", self.decoder_block_flops(B, T, N)):
-                Q0, Kd, Vd = dec.project_q_kv(P, pf0, N, tok, B * T, K, row_map=(K, Lt, 4))
-            paired = (pf0, Q0)
-        else:
-            with span("stage:decoder_cross_attn_block", self.decoder_block_flops(B, T, N)):
-                Kd, Vd = dec.project_kv(P, tok, B * T, K, row_map=(K, Lt, 4))       # latent tokens 4..4+K of every frame
-        for b in range(B):
-            for n0 in range(0, N, nchunk):
-                n1 = min(N, n0 + nchunk)
-                if hoisted is not None:
-                    pf, Q = hoisted[b]
-                elif paired is not None:
-                    pf, Q = paired
-                else:
-                    pf = self._point_features(P, pcd[b, n0:n1], nrm[b, n0:n1].contiguous(), rgb[b, n0:n1].contiguous())
-                with span("stage:decoder_cross_attn_block", 0.0):
-                    x, fold_d = self.decoder_block(P, Kd[b * T:(b + 1) * T], Vd[b * T:(b + 1) * T], pf,
-                                                   None if (hoisted is None and paired is None) else Q)
-                if cap is not None and n0 == 0 and n1 == N:
-                    cap.setdefault("decoder_out_t0", []).append(x[:N].clone())
-                if fold_d is not None:
-                    # the head's LayerNorm rides in its first GEMM: statistics left by the MLP's last epilogue
-                    hw, hcs, hb = P.folded(head_ln.weight, head_ln.bias, head_fc1.weight, head_fc1.bias)
-                    h, lnk = fold_d.xb, dict(ln=fold_d.ln(head_ln.eps, hcs))
-                else:
-                    h = torch.empty(x.shape, dtype=P.dtype, device=dev)
-                    ops.layernorm(x, P.vec(head_ln.weight), P.vec(head_ln.bias), head_ln.eps, h)
-                    hw, hb, lnk = P.mat(head_fc1.weight), P.vec(head_fc1.bias), {}
-                whole = n0 == 0 and n1 == N
-                o = out[b] if whole else torch.empty((T, n1 - n0, 3), dtype=torch.float32, device=dev)
-                if FUSE_HEAD_N3 and P.dtype == torch.bfloat16 and C % 256 == 0 and not torch.is_grad_enabled():
-                    # Linear -> GELU -> Linear(C -> 3) without the [rows, C] intermediate: the first GEMM's epilogue contracts
-                    # its GELU output with the 3 x C weight and leaves C / 64 partial sums per row (M324_AUX_N3)
-                    part = torch.empty((C // 64, x.shape[0], 3), dtype=torch.float32, device=dev)
-                    ops.gemm(h, hw, None, bias=hb, act=ACT_GELU, n3=(w3, part), **lnk)
-                    ops.n3_finish(part, b3, o)
-                else:
-                    h2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
-                    ops.gemm(h, hw, h2, bias=hb, act=ACT_GELU, **lnk)
-                    ops.linear_n3(h2, w3, b3, o)
-                if not whole:
-                    out[b, :, n0:n1] = o
-        if cap is not None and "decoder_out_t0" in cap:
-            cap["decoder_out_t0"] = torch.stack(cap["decoder_out_t0"], dim=0)
+        latent = None
+        if keep_latent:
+            # rows 4..4+K of every frame, compact: ONE strided row copy (m324_cast fp32 -> fp32 over [B*T, Lt*C] rows)
+            latent = torch.empty((B * T, K * C), dtype=torch.float32, device=dev)
+            ops.cast(tok.view(B * T, Lt * C)[:, 4 * C:(4 + K) * C], torch.float32, out=latent)
+            latent = latent.view(B, T, K, C)
+        if encode_only:
+            return edict(input_data=sample, latent=latent)
+        out = self._decode(P, sample, tok, (K, Lt, 4), B, T, hoisted, cap)
 
         if shard is not None and parallel.collectives_on(shard[1]):
             rank, world, group = shard[:3]
@@ -730,6 +892,8 @@ class Motion_Latent_Model(nn.Module):
             else:
                 out = torch.cat([parts[r, :f] for r, f in enumerate(frames)], dim=0).transpose(0, 1).contiguous()
         result = edict(input_data=sample, pcd_moved=out)
+        if latent is not None:
+            result.latent = latent
         if keep_reuse:
             Ld = 1 + Pn
             anchor = dino_x[:Ld] if B == 1 else dino_x.view(B, T, Ld, C)[:, 0].reshape(B * Ld, C).contiguous()

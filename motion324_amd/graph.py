@@ -28,15 +28,16 @@ from . import prepared
 from .prepared import compute_dtype
 
 _KEYS = ("ref_shape_pcd", "ref_shape_normals", "ref_shape_rgbs", "ref_pcd", "ref_normal", "ref_rgb", "rgb_video",
-         "point_clouds", "m324_mesh_tokens", "m324_anchor_tokens")
-_FLAGS = ("m324_keep_reuse",)          # non-tensor entries of a sample that change what the forward returns
+         "point_clouds", "m324_mesh_tokens", "m324_anchor_tokens", "m324_latent")
+# non-tensor entries of a sample that change what the forward returns (m324_encode_only: also where it ends)
+_FLAGS = ("m324_keep_reuse", "m324_keep_latent", "m324_encode_only")
 
 
 def shape_key(sample) -> Tuple:
     """what a captured graph is specialised on besides weights and precision: every input's shape, whether the frames are
     bytes (m324_patchify_u8) or fp32, and the flags"""
     return tuple((k, tuple(sample[k].shape)) for k in _KEYS if k in sample) + \
-        (("u8", sample["rgb_video"].dtype == torch.uint8),) + tuple((f, bool(sample.get(f, False))) for f in _FLAGS)
+        (("u8", "rgb_video" in sample and sample["rgb_video"].dtype == torch.uint8),) + tuple((f, bool(sample.get(f, False))) for f in _FLAGS)
 
 
 def _static_copy(k: str, t: torch.Tensor) -> torch.Tensor:
@@ -214,7 +215,11 @@ class GraphedForward:
                 if src.data_ptr() != buf.data_ptr():
                     buf.copy_(src, non_blocking=True)
         g.replay()
-        out = edict(input_data=sample, pcd_moved=static_out["pcd_moved"])
+        out = edict(input_data=sample)
+        if "pcd_moved" in static_out:                # (absent from an encode-only forward)
+            out.pcd_moved = static_out["pcd_moved"]
+        if "latent" in static_out:                   # static buffer: a caller that keeps it clones it (encode_motion does)
+            out.latent = static_out["latent"]
         if "loss_metrics" in static_out:
             out.loss_metrics = static_out["loss_metrics"]
         if "reuse" in static_out:                    # static buffers like pcd_moved: overwritten by this graph's next replay

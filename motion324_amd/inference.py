@@ -83,6 +83,17 @@ def merge_windows(outs: torch.Tensor, out_map: List[Slot], ref_pcd: torch.Tensor
     return merged.unsqueeze(0)
 
 
+def merge_latents(lats: torch.Tensor, out_map: List[Slot]):
+    """lats [n_windows, C, K, d] (the windows' latents) -> (tokens [1, len(out_map), K, d], from_ref): the gather of
+    merge_windows on the latent.  from_ref lists the frames whose trajectory the merge rules overwrite with ref_pcd; their
+    token rows hold window 0's anchor frame and are never decoded."""
+    nW, C = lats.shape[0], lats.shape[1]
+    flat = [0 if s is None else s[0] * C + s[1] for s in out_map]
+    idx = torch.tensor(flat, dtype=torch.long).to(lats.device)
+    tokens = lats.reshape(nW * C, *lats.shape[2:]).index_select(0, idx)
+    return tokens.unsqueeze(0), [t for t, s in enumerate(out_map) if s is None]
+
+
 def _cfg_get(cfg, key, default=None):
     return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
 
@@ -196,7 +207,8 @@ def _native(model) -> bool:
 
 
 def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor: torch.Tensor, config, device,
-                        group=None, pipelined: Optional[bool] = None, reuse: Optional[bool] = None) -> Optional[torch.Tensor]:
+                        group=None, pipelined: Optional[bool] = None, reuse: Optional[bool] = None,
+                        return_latent: bool = False):
     """Same contract as the reference driver: video_tensor [T,H,W,3] in [0,1] (any T) -> trajectories [1,T,N,3]
     fp32 on `device`.  With an initialised process group the windows are sharded over its ranks and the result is
     available on every rank.
@@ -207,7 +219,11 @@ def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor
     a quarter of the host-to-device bytes).  reuse (None: with this package's model): the shape encoder's latent tokens and
     the anchor frame's image tokens are computed by the first window and handed to the others (Motion_Latent_Model._forward:
     `m324_mesh_tokens`, `m324_anchor_tokens`) -- they are the same in every window, bit for bit; the result equals the plain
-    loop's exactly (tests/test_configs_gpu.py)."""
+    loop's exactly (tests/test_configs_gpu.py).
+
+    return_latent (this package's model): returns (trajectories, MotionLatent) -- the video's motion latent, tokens
+    [1, T, K, d] gathered from the windows' latents by the same plan as the trajectories and all-gathered over the ranks like
+    them, `from_ref` = the frames the merge rules overwrite with ref_pcd; decode_video_latent moves another mesh by it."""
     tr = _cfg_get(config, "training")
     chunk = _cfg_get(tr, "frames", 12)
     use_amp = _cfg_get(tr, "use_amp", False)
@@ -227,9 +243,15 @@ def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor
     rank, world = parallel.world_info(group)
     mine = list(parallel.partition(len(windows), world, rank))
 
+    lats = []
+
     def check(out) -> torch.Tensor:
         if not (isinstance(out, dict) and "pcd_moved" in out):
             raise RuntimeError("model returned no pcd_moved")
+        if return_latent:
+            if "latent" not in out:
+                raise RuntimeError("model returned no latent: return_latent needs this package's model (`m324_keep_latent`)")
+            lats.append(out["latent"].float()[0])
         return out["pcd_moved"].float()[0]
 
     def call(sample):
@@ -242,6 +264,8 @@ def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor
             sample = dict(input_data)
             frames = video_tensor.index_select(0, idx)[None]
             sample["rgb_video"] = (frames if frames.dtype == torch.uint8 else frames.float()).to(device)
+            if return_latent:
+                sample["m324_keep_latent"] = True
             return check(call(sample))
         outs = [forward_window(w) for w in mine]
     else:
@@ -263,6 +287,8 @@ def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor
                 sample["m324_mesh_tokens"] = kept[0]
             elif reuse and len(mine) > 1:
                 sample["m324_keep_reuse"] = True
+            if return_latent:
+                sample["m324_keep_latent"] = True
             out = call(sample)
             feeder.release(slot)
             if kept is None and reuse and len(mine) > 1:
@@ -271,4 +297,26 @@ def run_model_inference(model, input_data: Dict[str, torch.Tensor], video_tensor
                 slot = feeder.upload(frames_of(mine[i + 1]))
             outs.append(check(out))
     local = torch.stack(outs, dim=0) if outs else torch.zeros((0, len(windows[0]), N, 3), dtype=torch.float32, device=device)
-    return merge_windows(parallel.all_gather_items(local, len(windows), group), out_map, ref_pcd.to(device))
+    merged = merge_windows(parallel.all_gather_items(local, len(windows), group), out_map, ref_pcd.to(device))
+    if not return_latent:
+        return merged
+    from .latent import MotionLatent
+    K, d = (model.num_learnable_tokens, model.embed_dim) if _native(model) else tuple(lats[0].shape[1:])
+    lat = torch.stack(lats, dim=0) if lats else torch.zeros((0, len(windows[0]), K, d), dtype=torch.float32, device=device)
+    tokens, from_ref = merge_latents(parallel.all_gather_items(lat, len(windows), group), out_map)
+    return merged, MotionLatent(tokens, d=d, K=K, frames=chunk, from_ref=from_ref)
+
+
+def decode_video_latent(model, latent, input_data: Dict[str, torch.Tensor], config, device) -> torch.Tensor:
+    """The trajectories [1, T, N, 3] of input_data's mesh (`ref_pcd`, `ref_normal`, `ref_rgb`) under a video's latent
+    (run_model_inference(..., return_latent=True)): every frame through the decoder and the head only, in passes of at most
+    M324_DECODE_ROWS (frame, point) rows; the frames in `latent.from_ref` become the mesh's ref_pcd as in the driver's merge."""
+    tr = _cfg_get(config, "training")
+    use_amp = _cfg_get(tr, "use_amp", False)
+    dev_type = torch.device(device).type
+    pts = [input_data[k].to(device) for k in ("ref_pcd", "ref_normal", "ref_rgb")]
+    with torch.no_grad(), torch.autocast(enabled=bool(use_amp), device_type=dev_type, dtype=torch.bfloat16):
+        out = model.decode_motion(latent.to(device), *pts)
+    for t in latent.from_ref:
+        out[0, t] = pts[0].reshape(-1, 3).to(out.dtype)
+    return out
