@@ -50,8 +50,8 @@ int m324_last_error(char* buf, int n);
 /* Fills name with the device's gcnArchName ("gfx950..."), returns CU count or negative status. */
 int m324_device_info(char* name, int n);
 /* Lab / test hook (not used by the product path): the kernel choosers' A/B switches -- "M324_GEMM" (forced schedule
- * number, 0 = automatic), "M324_GEMM_TN", "M324_XCD", "M324_ATTN_NW", "M324_ATTN_FLAT", "M324_ATTN_OCC", "M324_ATTN_NQ2",
- * "M324_ATTN_BWD_NW", "M324_ATTN_EXP", "M324_LN_ROWS", "M324_GEMM_PERSIST" -- are read from the environment ONCE, when the library is loaded; this call
+ * number, 0 = automatic), "M324_GEMM_TN", "M324_XCD", "M324_ATTN_NW", "M324_ATTN_BWD_NW", "M324_ATTN_EXP", "M324_LN_ROWS",
+ * "M324_GEMM_PERSIST", ... (the table in csrc/runtime.hip) -- are read from the environment ONCE, when the library is loaded; this call
  * overrides one of them afterwards (value INT_MIN restores the default).  No launch path calls getenv(). */
 int m324_set_tunable(const char* name, int value);
 

@@ -76,7 +76,8 @@ __device__ __forceinline__ void store_row_chunks(const f32x16 (&acc)[2], float m
 // PRESCALED: Q already carries scale * log2(e) (m324_qkv_split's q_scale), so scores are log2-domain.
 // NQ: 32-row query blocks per wave (1 or 2).  With NQ = 2 every K / Vt fragment read from LDS feeds two
 // MFMAs, a wave issues 32 MFMAs per barrier instead of 16, and the two blocks' softmax chains are
-// independent, so the scheduler can run one block's exp2 / pack work under the other block's MFMAs.
+// independent, so the scheduler can run one block's exp2 / pack work under the other block's MFMAs.  (Measured slower than
+// NQ = 1 -- 254 registers, one wave per SIMD -- and no longer instantiated; the parameter stays in the kernel's name.)
 // NWV: waves per workgroup (4 or 8).  Eight waves = 256 queries share every K / Vt tile, which halves the LDS-DMA
 // pieces per FLOP (the texture path is ~90 % busy at four waves) and, for the 10 368-token global attention, turns
 // 972 workgroups on 768 slots (two rounds, the second a quarter full) into 492 on 256 slots (1.92 rounds).
@@ -98,7 +99,7 @@ template <bool PRESCALED, int NQ, int NWV, bool VROW = false, int NST = 3>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 || NST == 2) ? 4 : 1)) void attn_bf16_kernel(const bf16_t* __restrict__ Q, long q_bstride,
                                                         const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
                                                         bf16_t* __restrict__ O, long ldo, int H, int Lq, int Lk,
-                                                        int Lkp, float scale_log2e, float* __restrict__ lse, int nqt, int xflags) {
+                                                        int Lkp, float scale_log2e, float* __restrict__ lse, int nqt) {
     // [stage][K | Vt]; the one-tile form appends a wave-private 4-KiB block per wave for the whole-row output stores (its only
     // stage is still being read by the slower waves when the first one is done; 32 KiB keeps four workgroups per CU)
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * ASTAGE + (NST == 1 ? NWV * 4096 : 0)];
@@ -184,10 +185,6 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
     const int nt = (Lk + KV - 1) / KV;
     issue_tile(0);
     if (NST != 2 && nt > 1) issue_tile(1);
-    // Static priority for the second-dispatched half of an 8-wave workgroup (experiment switch M324_ATTN_EXP bit 0): the
-    // younger wave of a SIMD loses every VALU arbitration against its older partner (microarch guide, "two waves per SIMD",
-    // item 4); one s_setprio for the whole loop, no per-segment flips.
-    if (NWV == 8 && (xflags & 1) && wave >= 4) __builtin_amdgcn_s_setprio(1);
     // lane part of a K / Vt fragment address: row l31 of a 32-row block, chunk hi swizzled by the row.  k-step ks toggles
     // chunk bits 1-2, i.e. XORs the byte offset with ks << 5, and the stage base (a multiple of 16 KiB) can be added
     // before that XOR: one v_add per tile + one v_xor per read replace the full swizzle arithmetic per read (35 of the
@@ -350,7 +347,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
 
         }
     };
-    if (NWV == 4 && NQ == 1 && NST == 3 && (qt + 1) * NWV * QW > Lq && !(xflags & 4)) tiles(std::true_type{});      // M324_ATTN_EXP bit 2: A/B
+    if (NWV == 4 && NQ == 1 && NST == 3 && (qt + 1) * NWV * QW > Lq) tiles(std::true_type{});
     else tiles(std::false_type{});
 
     // ---- normalise and store.  o[n][db][r]: d = db*32 + (r&3) + 8*(r>>2) + 4*hi, q = l31
@@ -384,21 +381,15 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
                     c[k] = sw[1];
                 }
                 const int chunk = db * 4 + 2 * gp + hi;
-                if (NST == 1 && (xflags & 2)) {  // A/B (M324_ATTN_EXP bit 1): round 2's direct 16-byte stores of the one-tile form
-                    if (q < Lq) *reinterpret_cast<uint4*>(O + ((long)b * Lq + q) * ldo + h * 64 + chunk * 8) = make_uint4(a[0], a[1], c[0], c[1]);
-                } else {
-                    *reinterpret_cast<uint4*>(scr + l31 * 128 + ((chunk ^ (l31 & 7)) << 4)) = make_uint4(a[0], a[1], c[0], c[1]);
-                }
+                *reinterpret_cast<uint4*>(scr + l31 * 128 + ((chunk ^ (l31 & 7)) << 4)) = make_uint4(a[0], a[1], c[0], c[1]);
             }
-        if (!(NST == 1 && (xflags & 2))) {
-            const int r8 = lane >> 3, c8 = lane & 7;
-            bf16_t* obase = O + ((long)b * Lq + q0 + n * QW) * ldo + h * 64 + c8 * 8;
+        const int r8 = lane >> 3, c8 = lane & 7;
+        bf16_t* obase = O + ((long)b * Lq + q0 + n * QW) * ldo + h * 64 + c8 * 8;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int r = p * 8 + r8;
-                const uint4 v = *reinterpret_cast<const uint4*>(scr + r * 128 + ((c8 ^ (r & 7)) << 4));
-                if (q0 + n * QW + r < Lq) *reinterpret_cast<uint4*>(obase + (long)r * ldo) = v;
-            }
+        for (int p = 0; p < 4; ++p) {
+            const int r = p * 8 + r8;
+            const uint4 v = *reinterpret_cast<const uint4*>(scr + r * 128 + ((c8 ^ (r & 7)) << 4));
+            if (q0 + n * QW + r < Lq) *reinterpret_cast<uint4*>(obase + (long)r * ldo) = v;
         }
     }
 }
@@ -1085,73 +1076,62 @@ void m324_attn_pwg_launch(const void* Q, long q_bstride, const void* K, const vo
 enum AttnFamily { ATTN_F32, ATTN_PWG, ATTN_PWG_BOUNDED, ATTN_FRAMES, ATTN_BF16 };
 struct AttnPlan {
     AttnFamily family;
-    bool ps, vrow;               // ATTN_BF16: attn_bf16_kernel<PS, NQ, NW, VROW, NST>; ATTN_FRAMES: ps = nontemporal stores
-    int nq, nw, nst;
+    bool ps, vrow;               // ATTN_BF16: attn_bf16_kernel<PS, 1, NW, VROW, NST>
+    int nw, nst;
     dim3 grid;
-    unsigned threads, lds_pad;
+    unsigned threads;
     int nqt;                     // > 0: flat grid of nqt query tiles per (batch, head)
 };
 
 // flags: M324_ATTN_*, and 256 = the queries are shared by the batches (q_bstride == 0)
 static AttnPlan attn_plan(int B, int H, int Lq, int Lk, int flags, int dtype) {
     AttnPlan p{};
-    p.nq = 1, p.nw = NW, p.nst = 3, p.threads = 256;
+    p.nw = NW, p.nst = 3, p.threads = 256;
     p.grid = dim3(ceil_div(Lq, QB), H, B);
     if (dtype != M324_BF16) {
         p.family = ATTN_F32;
         return p;
     }
     const bool vrow = (flags & M324_ATTN_V_ROWMAJOR) != 0, ps = (flags & M324_ATTN_Q_PRESCALED) != 0;
-    // NQ = 2 (two query blocks per wave) measured slower than NQ = 1 on MI355X (254 VGPRs -> one wave per
-    // SIMD); it stays selectable for experiments only.
-    const bool nq2 = m324::tunable(m324::TUN_ATTN_NQ2) != 0 && Lq >= 1024 && !vrow;
     // eight waves per workgroup for long query sets (M324_ATTN_NW=4|8 forces: A/B runs, tests)
     const int fnw = m324::tunable(m324::TUN_ATTN_NW);
-    const bool w8 = !nq2 && (fnw ? fnw == 8 : (Lq >= 2048 && Lk >= 512));
+    const bool w8 = fnw ? fnw == 8 : (Lq >= 2048 && Lk >= 512);
     // M324_ATTN_PWG=0: the eight-wave kernel below (A/B runs, tests)
-    if (m324::tunable(m324::TUN_ATTN_PWG) != 0 && ps && !vrow && !nq2 && fnw == 0 && Lq >= 2048 && Lk >= 512) {
+    if (m324::tunable(m324::TUN_ATTN_PWG) != 0 && ps && !vrow && fnw == 0 && Lq >= 2048 && Lk >= 512) {
         p.family = (flags & M324_ATTN_SCORES_BOUNDED) ? ATTN_PWG_BOUNDED : ATTN_PWG;
         p.grid = dim3((unsigned)((long)ceil_div(Lq, 256) * H * B));      // (m324_attention checks that it fits)
         return p;
     }
-    p.family = ATTN_BF16, p.ps = ps, p.vrow = vrow, p.nq = nq2 ? 2 : 1, p.nw = w8 ? 8 : 4, p.threads = p.nw * 64;
-    p.grid.x = ceil_div(Lq, (nq2 || w8) ? 2 * QB : QB);
-    // XCD-aware flat grid for the 8-wave kernel (M324_ATTN_FLAT=0 keeps the 3-D grid: A/B runs)
+    p.family = ATTN_BF16, p.ps = ps, p.vrow = vrow, p.nw = w8 ? 8 : 4, p.threads = p.nw * 64;
+    p.grid.x = ceil_div(Lq, w8 ? 2 * QB : QB);
+    // XCD-aware flat grid for the 8-wave kernel.
     // The same flat order for the short sequences with several query tiles per (batch, head) -- the per-frame blocks:
     // 324 / 257 tokens = 3 tiles of 128 queries that walk the SAME K / V.  On the 3-D grid they are consecutive
     // workgroup ids, i.e. they land on three different XCDs and each pulls the head's K / V through its own L2
     // (round 2 counters: 111.8 MB moved for 55.8 MB algorithmic); on the flat grid they are neighbours in ONE XCD's
-    // list.  M324_ATTN_FLAT=2 restricts the flat grid to the 8-wave kernel again (A/B runs).
-    const int flat = m324::tunable(m324::TUN_ATTN_FLAT);
-    const bool one_tile = ps && !w8 && !nq2 && !vrow && Lk <= KV;
-    if (flat != 0 && (w8 || (flat != 2 && !nq2 && !one_tile && p.grid.x > 1 && (long)p.grid.x * H * B >= 512))) {
+    // list.
+    const bool one_tile = ps && !w8 && !vrow && Lk <= KV;
+    if (w8 || (!one_tile && p.grid.x > 1 && (long)p.grid.x * H * B >= 512)) {
         p.nqt = (int)p.grid.x;
         p.grid = dim3(p.grid.x * H * B, 1, 1);
     }
-    const int occ = m324::tunable(m324::TUN_ATTN_OCC), xfl = m324::tunable(m324::TUN_ATTN_EXP);
-    if (ps && !w8 && Lk > KV && Lk <= 16 * KV && occ != 3) {
+    if (ps && !w8 && Lk > KV && Lk <= 16 * KV) {
         // per-frame blocks (round 6; row-major V from the fused q|k|v epilogue or the training step's transposed Vt, pre-scaled q, four
         // waves, a handful of key tiles): four workgroups per CU instead of three (two LDS stages, 128 registers); microbench, interleaved
-        // A/B on one box: L = 324 26.6 -> 24.5 us, L = 257 22.6 -> 21.2 us; M324_ATTN_OCC=3 keeps the three-stage form (A/B)
+        // A/B on one box: L = 324 26.6 -> 24.5 us, L = 257 22.6 -> 21.2 us
         p.nst = 2;
-    } else if (one_tile && (flags & 256) && B % 2 == 0 && Lq >= 512 && !(xfl & 8)) {
-        // shared queries under several batches of one key tile (the decoder): two frames per workgroup (M324_ATTN_EXP bit 3: A/B;
-        // bit 4: plain stores)
-        p.family = ATTN_FRAMES, p.ps = !(xfl & 16);
+    } else if (one_tile && (flags & 256) && B % 2 == 0 && Lq >= 512 && m324::tunable(m324::TUN_ATTN_EXP) != 8) {
+        // shared queries under several batches of one key tile (the decoder): two frames per workgroup, nontemporal stores
+        // (M324_ATTN_EXP=8: one workgroup per frame in the one-tile form below -- the parity test's other arm)
+        p.family = ATTN_FRAMES;
         p.grid.z = B / 2;
-    } else if (one_tile && occ != 1) {               // one tile (M324_ATTN_OCC=1: A/B)
+    } else if (one_tile) {
         p.nst = 1;
-    } else if (occ == 2) {
-        // Co-residency: the NQ = 1 kernel fits 3 workgroups per CU (168 VGPRs, 32 KiB LDS).  Interleaved A/B on
-        // MI355X: 3 per CU beats 2 per CU (422 vs 453 us on the 10 368-token global attention) even though the
-        // grid then ends in a partly filled round -- latency hiding wins over round quantisation.
-        // M324_ATTN_OCC=2 pads the LDS allocation to force two per CU (experiments only).
-        p.lds_pad = 24 * 1024;
     }
     return p;
 }
 
-static constexpr int attn_key(bool ps, int nq, int nw, bool vrow, int nst) { return (int)ps | nq << 1 | nw << 3 | (int)vrow << 7 | nst << 8; }
+static constexpr int attn_key(bool ps, int nw, bool vrow, int nst) { return (int)ps | nw << 1 | (int)vrow << 5 | nst << 6; }
 
 extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B,
                               int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, void* stream) {
@@ -1166,12 +1146,11 @@ extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, cons
     hipStream_t s = (hipStream_t)stream;
     const float sl = (q_prescaled & M324_ATTN_Q_PRESCALED) ? 1.0f : scale * LOG2E;
     const AttnPlan p = attn_plan(B, H, Lq, Lk, (q_prescaled & 7) | (q_bstride == 0 ? 256 : 0), dtype);
-    const int xfl = m324::tunable(m324::TUN_ATTN_EXP);
-#define M324_ATTN(PS, NQ, NWV, VROW, NST)                                                                               \
-    case attn_key(PS, NQ, NWV, VROW, NST):                                                                                   \
-        hipLaunchKernelGGL((attn_bf16_kernel<PS, NQ, NWV, VROW, NST>), p.grid, dim3(p.threads), p.lds_pad, s,           \
+#define M324_ATTN(PS, NWV, VROW, NST)                                                                                   \
+    case attn_key(PS, NWV, VROW, NST):                                                                                  \
+        hipLaunchKernelGGL((attn_bf16_kernel<PS, 1, NWV, VROW, NST>), p.grid, dim3(p.threads), 0, s,                    \
                            (const bf16_t*)Q, q_bstride, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, \
-                           Lkp, sl, lse, p.nqt, xfl);                                                                    \
+                           Lkp, sl, lse, p.nqt);                                                                         \
         break
     switch (p.family) {
         case ATTN_F32:
@@ -1184,23 +1163,19 @@ extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, cons
             m324_attn_pwg_launch(Q, q_bstride, K, Vt, O, ldo, B, H, Lq, Lk, lse, p.family == ATTN_PWG_BOUNDED, s);
             break;
         case ATTN_FRAMES:
-            if (p.ps)
-                hipLaunchKernelGGL((attn_frames_kernel<2, true>), p.grid, dim3(p.threads), 0, s, (const bf16_t*)Q,
-                                   (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, lse);
-            else
-                hipLaunchKernelGGL((attn_frames_kernel<2, false>), p.grid, dim3(p.threads), 0, s, (const bf16_t*)Q,
-                                   (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, lse);
+            hipLaunchKernelGGL((attn_frames_kernel<2, true>), p.grid, dim3(p.threads), 0, s, (const bf16_t*)Q,
+                               (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, Lkp, lse);
             break;
         case ATTN_BF16:
-            switch (attn_key(p.ps, p.nq, p.nw, p.vrow, p.nst)) {      // the instantiations that are built
-                M324_ATTN(true, 1, 4, false, 3); M324_ATTN(true, 1, 8, false, 3); M324_ATTN(true, 2, 4, false, 3);
-                M324_ATTN(false, 1, 4, false, 3); M324_ATTN(false, 1, 8, false, 3); M324_ATTN(false, 2, 4, false, 3);
-                M324_ATTN(true, 1, 4, true, 3); M324_ATTN(true, 1, 8, true, 3);
-                M324_ATTN(false, 1, 4, true, 3); M324_ATTN(false, 1, 8, true, 3);
-                M324_ATTN(true, 1, 4, false, 2); M324_ATTN(true, 1, 4, true, 2);       // per-frame blocks
-                M324_ATTN(true, 1, 4, false, 1);                                       // one key tile
+            switch (attn_key(p.ps, p.nw, p.vrow, p.nst)) {      // the instantiations that are built
+                M324_ATTN(true, 4, false, 3); M324_ATTN(true, 8, false, 3);
+                M324_ATTN(false, 4, false, 3); M324_ATTN(false, 8, false, 3);
+                M324_ATTN(true, 4, true, 3); M324_ATTN(true, 8, true, 3);
+                M324_ATTN(false, 4, true, 3); M324_ATTN(false, 8, true, 3);
+                M324_ATTN(true, 4, false, 2); M324_ATTN(true, 4, true, 2);       // per-frame blocks
+                M324_ATTN(true, 4, false, 1);                                    // one key tile
                 default:
-                    M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention: attn_bf16_kernel<%d, %d, %d, %d, %d> is not built", (int)p.ps, p.nq, p.nw,
+                    M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention: attn_bf16_kernel<%d, 1, %d, %d, %d> is not built", (int)p.ps, p.nw,
                               (int)p.vrow, p.nst);
             }
             break;
@@ -1221,8 +1196,8 @@ extern "C" int m324_attention_plan(int B, int H, int Lq, int Lk, int flags, int 
         case ATTN_F32: snprintf(name, sizeof(name), "attn_f32_kernel"); break;
         case ATTN_PWG: snprintf(name, sizeof(name), "attn_pwg_kernel"); break;
         case ATTN_PWG_BOUNDED: snprintf(name, sizeof(name), "attn_pwg_bounded_kernel"); break;
-        case ATTN_FRAMES: snprintf(name, sizeof(name), "attn_frames_kernel<2, %s>", tf[p.ps]); break;
-        case ATTN_BF16: snprintf(name, sizeof(name), "attn_bf16_kernel<%s, %d, %d, %s, %d>", tf[p.ps], p.nq, p.nw, tf[p.vrow], p.nst); break;
+        case ATTN_FRAMES: snprintf(name, sizeof(name), "attn_frames_kernel<2, true>"); break;
+        case ATTN_BF16: snprintf(name, sizeof(name), "attn_bf16_kernel<%s, 1, %d, %s, %d>", tf[p.ps], p.nw, tf[p.vrow], p.nst); break;
     }
     snprintf(buf, (size_t)n, "%s grid=%ldx%ux%u", name, (long)p.grid.x * p.threads, p.grid.y, p.grid.z);
     return p.family == ATTN_F32 ? 0 : p.nw;

@@ -33,9 +33,9 @@ void m324_set_error(const char* fmt, ...);
 // (M324_GEMM=v10, M324_ATTN_NW=8, ...); afterwards only m324_set_tunable() changes them (labs / tests).  No launch
 // path calls getenv().
 namespace m324 {
-enum Tunable { TUN_GEMM = 0, TUN_GEMM_TN, TUN_XCD, TUN_ATTN_NW, TUN_ATTN_FLAT, TUN_ATTN_OCC, TUN_ATTN_NQ2, TUN_ATTN_BWD_NW,
-               TUN_ATTN_EXP, TUN_LN_ROWS, TUN_GEMM_PERSIST, TUN_ATTN_PWG, TUN_QKV_RING, TUN_NT_MB, TUN_HP, TUN_COUNT };
-int tunable(int which);          // 0 = "not set" for every switch except TUN_XCD (default 3) / TUN_ATTN_FLAT (default 1)
+enum Tunable { TUN_GEMM = 0, TUN_GEMM_TN, TUN_XCD, TUN_ATTN_NW, TUN_ATTN_BWD_NW, TUN_ATTN_EXP, TUN_LN_ROWS, TUN_GEMM_PERSIST, TUN_ATTN_PWG,
+               TUN_QKV_RING, TUN_NT_MB, TUN_HP, TUN_COUNT };
+int tunable(int which);          // the value of a switch; csrc/runtime.hip kTun holds the defaults
 int cu_count();                  // compute units of the current device, queried once; 256 (an MI355X) when no device is visible
 }  // namespace m324
 

@@ -349,7 +349,6 @@ __device__ __forceinline__ void gemm_ring_body(unsigned char* __restrict__ ring_
     tile_setup(blockIdx.x);
     // (live = false: a look-ahead piece past the end of K -- counted, written, not fetched: gemm_tile.h dma_rsrc_none)
     const __amdgpu_buffer_rsrc_t rnone = dma_rsrc_none(A);
-    const bool refetch = (xcd_remap & 8) != 0;              // M324_XCD bit 3 (A/B): fetch the last stage again instead, as rounds 1-4 did
     auto issue2a = [&](int i0, int st, int pos, bool live = true) {
         unsigned char* d = ring_w + pos * CHUNK10 + wave * 4096 + i0 * 1024;
 #pragma unroll
@@ -423,7 +422,7 @@ __device__ __forceinline__ void gemm_ring_body(unsigned char* __restrict__ ring_
         pwn = pwn >= 5 ? pwn - 5 : pwn;
         pan = pan >= 5 ? pan - 5 : pan;
         const int sw = s + 1 < NS ? s + 1 : NS - 1, sa = s + 2 < NS ? s + 2 : NS - 1;
-        const bool wl = s + 1 < NS || refetch, al = s + 2 < NS || refetch;
+        const bool wl = s + 1 < NS, al = s + 2 < NS;
         load_frags(0, pa, pw, 0);
         if constexpr (ISSUE) issue2b(0, sw, pwn, wl);
         mma8(1);                                            // (s-1, k-step 3); zeros in the first iteration
@@ -535,7 +534,6 @@ __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long ld
     }
     const __amdgpu_buffer_rsrc_t ra = dma_rsrc(A + (long)m0 * lda), rb = dma_rsrc(W + (long)n0 * ldw);
     const __amdgpu_buffer_rsrc_t rnone = dma_rsrc_none(A);    // look-ahead pieces past the end of K: gemm_tile.h dma_rsrc_none
-    const bool refetch = (xcd_remap & 8) != 0;
     auto issue2 = [&](const unsigned (&g)[4], int i0, int st, int pos, bool live = true) {
         unsigned char* d = smem + pos * CHUNK13 + wave * 4096 + i0 * 1024;
         const bool isa = &g[0] == &ga[0];
@@ -582,7 +580,7 @@ __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long ld
     // in front of the ring's first pieces (gemm_tile.h res_prefetch; 64 registers, 226 of the 256 two workgroups per CU leave a wave)
     constexpr bool PRE_RES = RES == 1 && sizeof(TOUT) == 4;
     ResPre<2> pres;
-    const bool use_pres = PRE_RES && ep.residual != nullptr && (xcd_remap & 16) == 0;       // M324_XCD bit 4: A/B
+    const bool use_pres = PRE_RES && ep.residual != nullptr;
     if constexpr (PRE_RES) {
         if (use_pres) res_prefetch<2>(ep, M, N, m0 + wm * 64, n0 + wn * 64, lane, pres);
     }
@@ -606,7 +604,7 @@ __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long ld
         pwn = pwn >= 5 ? pwn - 5 : pwn;
         pan = pan >= 5 ? pan - 5 : pan;
         const int sw = s + 1 < NS ? s + 1 : NS - 1, sa = s + 2 < NS ? s + 2 : NS - 1;
-        const bool wl = s + 1 < NS || refetch, al = s + 2 < NS || refetch;
+        const bool wl = s + 1 < NS, al = s + 2 < NS;
         load_frags(0, pa, pw, 0);
         if constexpr (ISSUE) issue2(gb, 0, sw, pwn, wl);
         mma4(1);                                            // (s-1, k-step 3); zeros in the first iteration
@@ -1030,15 +1028,13 @@ static bool vec_ok(const m324_gemm_args* a) {
 // Tile-order mode of tile_of(): M324_XCD bit 0 = contiguous range per XCD, bit 1 = the 4 x 2 group order for weights that
 // do not fit an XCD's L2 beside the streaming A panels AND are wider than deep (q|k|v, fc1: measured HBM fetch -28 % / -13 %
 // at equal time; fc2's K = 3072 A panels dominate its traffic and the group order re-fetches them: +35 %), bit 2 = force
-// it (tests, lab), bit 3 = the ring kernels' look-ahead past the end of K fetches the last stage again instead of nothing (A/B).  Default 3.
+// it (tests, lab).  Default 3.
 static int xcd_mode(const m324_gemm_args* a) {
     const int t = m324::tunable(m324::TUN_XCD);
-    const int old_refetch = t & (8 | 16);        // A/B bits handed through to the kernels: 3 = look-ahead pieces past the end of K fetch the
-                                                 // last stage again (rounds 1-4); 4 = v12 without the residual prefetch (round 6)
-    if (!(t & 1)) return old_refetch;
+    if (!(t & 1)) return 0;
     const long wbytes = (long)a->N * a->K * (a->in_dtype == M324_BF16 ? 2 : 4);
-    if ((t & 4) || ((t & 2) && wbytes > (5l << 19) && a->N >= 2 * a->K)) return 3 | old_refetch;
-    return 1 | old_refetch;
+    if ((t & 4) || ((t & 2) && wbytes > (5l << 19) && a->N >= 2 * a->K)) return 3;
+    return 1;
 }
 
 // Kernel choice (pick_variant) and, around it, everything else one call launches (make_plan below).  The schedules:

@@ -52,7 +52,6 @@ __global__ __launch_bounds__(256) void gemm_ring4_kernel(const bf16_t* __restric
         rb = dma_rsrc(W + (long)n0 * ldw);
     };
     const __amdgpu_buffer_rsrc_t rnone = dma_rsrc_none(A);    // look-ahead pieces past the end of K: gemm_tile.h dma_rsrc_none
-    const bool refetch = (xcd_remap & 8) != 0;
     auto issue4 = [&](const unsigned (&g)[8], int i0, int st, int pos, bool live = true) {
         unsigned char* d = smem + pos * CHUNK10 + wave * 8192 + i0 * 1024;
         const bool isa = &g[0] == &ga[0];
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(256) void gemm_ring4_kernel(const bf16_t* __restric
         pwn = pwn >= 5 ? pwn - 5 : pwn;
         pan = pan >= 5 ? pan - 5 : pan;
         const int sw = s + 1 < NS ? s + 1 : NS - 1, sa = s + 2 < NS ? s + 2 : NS - 1;
-        const bool wl = s + 1 < NS || refetch, al = s + 2 < NS || refetch;
+        const bool wl = s + 1 < NS, al = s + 2 < NS;
         load_frags(0, pa, pw, 0);
         if constexpr (ISSUE) issue4(gb, 0, sw, pwn, wl);
         mma16(1);                                           // (s-1, k-step 3); zeros in the first iteration
@@ -215,7 +214,6 @@ __global__ __launch_bounds__(256) void gemm_ring3_kernel(const bf16_t* __restric
     }
     const __amdgpu_buffer_rsrc_t ra = dma_rsrc(A + (long)m0 * lda), rb = dma_rsrc(W + (long)n0 * ldw);
     const __amdgpu_buffer_rsrc_t rnone = dma_rsrc_none(A);    // look-ahead pieces past the end of K: gemm_tile.h dma_rsrc_none
-    const bool refetch = (xcd_remap & 8) != 0;
     auto issue3 = [&](int i0, int st, int slot, bool live = true) {           // pieces i0 .. i0+2 of stage st
         unsigned char* base = smem + slot * STAGE12;
 #pragma unroll
@@ -268,7 +266,7 @@ __global__ __launch_bounds__(256) void gemm_ring3_kernel(const bf16_t* __restric
     // are older than every ring piece, so the counted waits below retire them with stage 0.
     constexpr bool PRE_RES = RES == 1 && sizeof(TOUT) == 4;
     ResPre<4> pres;
-    const bool use_pres = PRE_RES && ep.residual != nullptr && (xcd_remap & 16) == 0;       // bit 4: A/B (M324_XCD)
+    const bool use_pres = PRE_RES && ep.residual != nullptr;
     if constexpr (PRE_RES) {
         if (use_pres) res_prefetch<4>(ep, M, N, m0 + wm * 128, n0 + wn * 64, lane, pres);
     }
@@ -286,7 +284,7 @@ __global__ __launch_bounds__(256) void gemm_ring3_kernel(const bf16_t* __restric
         constexpr bool ISSUE = decltype(issue_tag)::value;
         const int fslot = slot == 0 ? 2 : slot - 1;         // (s + 2) % 3 == (s - 1) % 3
         const int sn = s + 2 < NS ? s + 2 : NS - 1;
-        const bool live = s + 2 < NS || refetch;
+        const bool live = s + 2 < NS;
         load_frags(0, slot, 0);
         if constexpr (ISSUE) issue3(0, sn, fslot, live);
         mma8(1);                                            // (s-1, k-step 3); zeros in the first iteration

@@ -28,10 +28,6 @@ HOST: Dict[str, Tuple[str, str, str]] = {
     "M324_FUSE_QKV": ("1", "transformer.FUSE_QKV", "bf16 inference: q|k|v projection epilogue writes head-major Q / K / V (RMSNorm, pre-scale)"),
     "M324_FUSE_QKV_VT": ("1", "transformer.FUSE_QKV_VT", "the same for long sequences: the epilogue writes the transposed, key-permuted V"),
     "M324_TRAIN_STORE": ("1", "training.TRAIN_STORE", "training: the forward keeps block internals while they fit half of the free HBM (0: always recompute, the reference's checkpoint policy)"),
-    "M324_TRAIN_DINO_FUSED": ("1", "training.DINO_FUSED", "training: the frozen DINOv2 encoder (no gradient flows through it) runs its inference form -- LayerNorm fold, fused q|k|v epilogue -- and is enqueued first in the step (0: the unfused form the trainable blocks use)"),
-    "M324_DIRECT_GRADS": ("1", "backward.DIRECT_GRADS", "training: weight / bias gradients are written straight into the optimizer's flat gradient buffer (0: temporary + copy)"),
-    "M324_ACC_GRADS": ("1", "backward.ACC_GRADS", "training: later gradients of a shared weight (the decoder's per-sample passes) are summed into the one it holds by the weight-gradient kernel's own reduction (0: temporary + torch add)"),
-    "M324_GELU_GRAD_FWD": ("1", "backward.GELU_GRAD_FWD", "training: the fc1 GEMM of every MLP leaves gelu'(z) next to gelu(z) (M324_AUX_STORE_GELU_GRAD) and the dgrad GEMM behind fc2 multiplies by it (M324_AUX_MUL); 0: it leaves z and the dgrad epilogue evaluates erf and exp again"),
     "M324_WEIGHT_MIRROR": ("1", "optim.WEIGHT_MIRROR", "training: FusedAdamW keeps bf16 row-major and transposed copies of every Linear weight in two flat buffers, rewritten by one m324_weight_mirror launch after each update (0: Prepared casts / m324_transpose per weight and step)"),
     "M324_DEFER_COLSUM": ("1", "ops.DEFER_COLSUM", "training: the sums of the weight gradients' split-K partials and of the norm-weight partials wait in a queue and leave in one m324_colsum_multi launch per block (0: one m324_colsum launch each, at once)"),
     "M324_MXFP8": ("0", "Pcd_motion.MXFP8_DEFAULT", "1: a model whose config names no model.inference_precision uses \"mxfp8\" -- block-scaled e4m3 operands for the GEMM roles of transformer.MX_ROLES (the trunk and DINOv2 q|k|v projections) in a bf16 inference forward (DESIGN section 4)"),
@@ -43,13 +39,10 @@ HOST: Dict[str, Tuple[str, str, str]] = {
 LIBRARY: Dict[str, Tuple[str, str]] = {
     "M324_GEMM": ("0", "force a GEMM schedule (v2 | v5 | v9 | v10 | v11 | v12 | v13 | v15); 0 = chooser"),
     "M324_GEMM_TN": ("0", "128: force the 128 x 128 weight-gradient kernel"),
-    "M324_XCD": ("3", "tile order: bit 0 XCD-contiguous ranges (NN GEMMs; the weight-gradient GEMM's (slice, tile) items since round 6), bit 1 4 x 2 group order for wide weights, bit 2 force it; bit 3: the ring GEMMs' look-ahead pieces past the end of K fetch the last stage again (rounds 1-4) instead of nothing (A/B); bit 4: the 256 x 128 kernel (v12) without the residual prefetch (A/B)"),
+    "M324_XCD": ("3", "tile order: bit 0 XCD-contiguous ranges (NN GEMMs; the weight-gradient GEMM's (slice, tile) items since round 6), bit 1 4 x 2 group order for wide weights, bit 2 force it"),
     "M324_ATTN_NW": ("0", "attention forward: waves per workgroup (4 | 8); 0 = by sequence length"),
-    "M324_ATTN_FLAT": ("1", "XCD-aware flat grid: 1 = global and per-frame attention, 2 = the 8-wave global attention only, 0 = 3-D grid"),
-    "M324_ATTN_OCC": ("0", "attention A/B: 1 = no one-tile form, 2 = two workgroups per CU (padded LDS), 3 = the per-frame attentions (row-major V, short sequences) keep the three-stage ring, three workgroups per CU (default since round 6: two stages, four per CU)"),
-    "M324_ATTN_NQ2": ("0", "attention: 64 queries per wave"),
     "M324_ATTN_BWD_NW": ("0", "attention backward: waves per workgroup -- 0 = four (the default since round 6), 8 = eight for both kernels, 84 = dQ eight + dK/dV four, 48 = the reverse, 2 = dQ with 64 queries per wave (A/B)"),
-    "M324_ATTN_EXP": ("0", "attention A/B bits: 1 static priority for the younger half of an 8-wave workgroup, 2 direct stores in the one-tile form, 4 no idle-wave skip in partly filled query tiles, 8 one workgroup per frame in the shared-query one-tile form, 16 its frame-pair form with plain (not nontemporal) stores"),
+    "M324_ATTN_EXP": ("0", "attention: 8 = one workgroup per frame in the shared-query one-tile form instead of the frame-pair kernel (the parity test's other arm)"),
     "M324_ATTN_PWG": ("1", "attention forward, long sequences: 1 = one wave per SIMD with the hand-placed stream (attention_pwg.hip), 0 = the eight-wave kernel"),
     "M324_QKV_RING": ("1", "128 x 128 chunk ring (v13) instead of the two-stage v2: bit 0 for the fused q|k|v projection (head-major epilogue), bit 1 for plain bf16 outputs (A/B)"),
     "M324_LN_ROWS": ("2", "LayerNorm: rows per wave (2 = two interleaved rows, 1 = one row: A/B)"),

@@ -46,7 +46,6 @@ def _point_features_bwd(model, P: Prepared, G: bw.GradStore, enc, feat, d_pf: to
     bw.linear_bwd(P, G, model.point_embed.mlp.weight, model.point_embed.mlp.bias, enc, demb, need_da=False)
 
 
-DINO_FUSED = switches.flag("M324_TRAIN_DINO_FUSED")          # the frozen image encoder runs its inference form inside a training step
 TRAIN_STORE = switches.get("M324_TRAIN_STORE")             # "1": keep block internals while they fit, "0": always recompute
 
 
@@ -132,11 +131,8 @@ def _forward_backward(model, sample: Dict[str, torch.Tensor], grad_scale: float 
     from .transformer import fusion_allowed
     video = _f32c(sample["rgb_video"])
     _, _, Hin, Win, _ = video.shape
-    if DINO_FUSED:
-        with fusion_allowed(), torch.no_grad():
-            dino_x = model.image_encoder.run(P, video.reshape(B * T, Hin, Win, 3), two_streams=False)
-    else:
-        dino_x = model.image_encoder.run(P, video.reshape(B * T, Hin, Win, 3))
+    with fusion_allowed(), torch.no_grad():
+        dino_x = model.image_encoder.run(P, video.reshape(B * T, Hin, Win, 3), two_streams=False)
 
     pts, enc_s, feat_s = _point_features_train(model, P, _f32c(sample["ref_shape_pcd"]).reshape(-1, 3),
                                                _f32c(sample["ref_shape_normals"]), _f32c(sample["ref_shape_rgbs"]))
@@ -199,8 +195,8 @@ def _forward_backward(model, sample: Dict[str, torch.Tensor], grad_scale: float 
         ops.layernorm(x, P.vec(head_ln.weight), P.vec(head_ln.bias), head_ln.eps, h)
         h2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
         if keep:
-            z2 = torch.empty(x.shape, dtype=P.dtype, device=dev)              # the pre-activation, or gelu' of it (M324_GELU_GRAD_FWD)
-            ops.gemm(h, P.mat(head_fc1.weight), h2, bias=P.vec(head_fc1.bias), act=ACT_GELU, **{"gelu_grad_out" if bw.GELU_GRAD_FWD else "preact_out": z2})
+            z2 = torch.empty(x.shape, dtype=P.dtype, device=dev)              # gelu' of the pre-activation
+            ops.gemm(h, P.mat(head_fc1.weight), h2, bias=P.vec(head_fc1.bias), act=ACT_GELU, gelu_grad_out=z2)
             head = (h, z2, h2)
         else:
             ops.gemm(h, P.mat(head_fc1.weight), h2, bias=P.vec(head_fc1.bias), act=ACT_GELU)
@@ -228,17 +224,9 @@ def _forward_backward(model, sample: Dict[str, torch.Tensor], grad_scale: float 
             h = torch.empty(x.shape, dtype=P.dtype, device=dev)
             ops.layernorm(x, P.vec(head_ln.weight), P.vec(head_ln.bias), head_ln.eps, h)
             z2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
-            if bw.GELU_GRAD_FWD:
-                h2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
-                ops.gemm(h, P.mat(head_fc1.weight), h2, bias=P.vec(head_fc1.bias), act=ACT_GELU, gelu_grad_out=z2)
-            else:
-                ops.gemm(h, P.mat(head_fc1.weight), z2, bias=P.vec(head_fc1.bias))
-                h2 = ops.gelu(z2)
-        if bw.GELU_GRAD_FWD:                                  # z2 holds gelu'(pre-activation): the 3-wide Linear's backward multiplies by it
-            dz2, dW3, db3 = ops.linear_n3_bwd(h2, w3, d_out[b], mul_by=z2)
-        else:
-            dh2, dW3, db3 = ops.linear_n3_bwd(h2, w3, d_out[b])
-            dz2 = ops.gelu_bwd(z2, dh2)
+            h2 = torch.empty(x.shape, dtype=P.dtype, device=dev)
+            ops.gemm(h, P.mat(head_fc1.weight), h2, bias=P.vec(head_fc1.bias), act=ACT_GELU, gelu_grad_out=z2)
+        dz2, dW3, db3 = ops.linear_n3_bwd(h2, w3, d_out[b], mul_by=z2)      # z2 holds gelu'(pre-activation): the backward multiplies by it
         G.add(head_fc2.weight, dW3)
         G.add(head_fc2.bias, db3)
         dh = bw.linear_bwd(P, G, head_fc1.weight, head_fc1.bias, h, dz2)

@@ -15,8 +15,9 @@ persistent grids are clamped to is the library's fallback of 256 on every machin
     python tests/golden/make_plan_table.py --stdout   prints the table instead
 
 Format: "plans" holds every distinct [return value, text] once; "gemm" / "attn" hold one index into it per case, in the order
-gemm_cases() / attn_cases() yield them; "key" is a digest of the case descriptions (a changed enumeration is told apart from a
-changed answer)."""
+gemm_cases() / attn_cases() yield them ("attn" packed: pack()); "key" is a digest of the case descriptions (a changed enumeration
+is told apart from a changed answer).  A plan that is in the file already keeps its index, so recording again changes the file
+only where cases or answers changed; loads() reads what dumps() wrote."""
 import ctypes as C
 import hashlib
 import importlib.util
@@ -33,9 +34,7 @@ GEMM_SHAPES = [(10368, 3072, 768), (10368, 2304, 768), (10368, 768, 3072), (1036
                (8224, 768, 3072), (2048, 1536, 768), (64, 768, 768), (293, 256, 192), (200, 128, 768), (300, 328, 64)]
 GEMM_SETTINGS = ([()] + [(("M324_GEMM", v),) for v in (1, 2, 5, 7, 9, 10, 11, 12, 13, 14, 15)] + [(("M324_HP", v),) for v in (0, 3)]
                  + [(("M324_QKV_RING", v),) for v in (0, 3)] + [(("M324_GEMM_PERSIST", 0),)])
-ATTN_SETTINGS = [()] + [((name, v),) for name, vals in (("M324_ATTN_NW", (4, 8)), ("M324_ATTN_FLAT", (0, 2)), ("M324_ATTN_OCC", (1, 2, 3)),
-                                                        ("M324_ATTN_NQ2", (1,)), ("M324_ATTN_EXP", (8, 16)), ("M324_ATTN_PWG", (0,)))
-                        for v in vals]
+ATTN_SETTINGS = [()] + [((name, v),) for name, vals in (("M324_ATTN_NW", (4, 8)), ("M324_ATTN_EXP", (8,)), ("M324_ATTN_PWG", (0,))) for v in vals]
 F32, BF16 = 0, 1
 AUX_STORE_PREACT, AUX_MUL_GELU_GRAD, AUX_HEADS, AUX_HEADS_VT, AUX_N3, AUX_STORE_GELU_GRAD, AUX_MUL = 1, 2, 3, 4, 5, 6, 7
 PTR = 4096                      # aligned stand-in: the queries read sizes, flags and alignments only
@@ -106,8 +105,10 @@ def gemm_cases():
 
 
 def attn_cases():
-    for setting, B, H, Lq, Lk, flags, dtype in itertools.product(ATTN_SETTINGS, (1, 2, 32), (1, 12), (1, 64, 257, 324, 512, 2048, 10368),
-                                                                 (1, 64, 257, 4096, 10368), (0, 1, 3, 5, 257), (BF16, F32)):
+    # (the key length innermost, the dtype outside the lengths: long runs of equal answers, which pack() stores as runs)
+    for setting, B, H, dtype, Lq, flags, Lk in itertools.product(ATTN_SETTINGS, (1, 2, 32), (1, 12), (BF16, F32),
+                                                                 (1, 64, 128, 257, 324, 512, 700, 1024, 2048, 4096, 10368),
+                                                                 (0, 1, 2, 3, 5, 257), (1, 37, 64, 257, 512, 1100, 4096, 10368)):
         yield setting, B, H, Lq, Lk, flags, dtype
 
 
@@ -119,17 +120,19 @@ def load_lib():
     return L
 
 
-def table():
+def table(keep=None):
+    """keep: the table recorded before (loads()); its plans keep their places"""
     L = load_lib()
     h = L.load()
     buf = C.create_string_buffer(256)
-    plans, index = [], {}
+    plans = [tuple(p) for p in keep["plans"]] if keep else []
+    index = {p: i for i, p in enumerate(plans)}
 
     def record(rc):
         key = (int(rc), buf.value.decode())
         if key not in index:
             index[key] = len(plans)
-            plans.append(list(key))
+            plans.append(key)
         return index[key]
 
     def answers(cases, ask):
@@ -151,24 +154,67 @@ def table():
 
     gemm, kg = answers(gemm_cases(), lambda shape, name, fields: h.m324_gemm_plan(C.byref(gemm_args(L, *shape, fields)), buf, 256))
     attn, ka = answers(attn_cases(), lambda *c: h.m324_attention_plan(*c, buf, 256))
-    # the most frequent answers get the shortest indices (a third of the file's size)
-    uses = [0] * len(plans)
-    for i in gemm + attn:
-        uses[i] += 1
-    order = sorted(range(len(plans)), key=lambda i: (-uses[i], i))
-    rank = {old: new for new, old in enumerate(order)}
-    return {"key": hashlib.sha256((kg + ka).encode()).hexdigest()[:16], "plans": [plans[i] for i in order],
-            "gemm": [rank[i] for i in gemm], "attn": [rank[i] for i in attn]}
+    # plans no case answers any more leave the list; the used ones past its new end move into their places, every other index stays
+    used = set(gemm) | set(attn)
+    n = len(used)
+    move = dict(zip((i for i in range(n, len(plans)) if i in used), (i for i in range(n) if i not in used)))
+    for i, hole in move.items():
+        plans[hole] = plans[i]
+    del plans[n:]
+    return {"key": hashlib.sha256((kg + ka).encode()).hexdigest()[:16], "plans": [list(p) for p in plans],
+            "gemm": [move.get(i, i) for i in gemm], "attn": [move.get(i, i) for i in attn]}
+
+
+def pack(idx, settings):
+    """Runs of equal answers.  The first (default) setting: [answer, count, ...]; every further setting: [position, count, answer, ...]
+    of the cases it answers differently from the default.  (The cases run setting by setting.)"""
+    n = len(idx) // settings
+    base, out = idx[:n], [[]]
+    for v in base:
+        if out[0] and out[0][-2] == v:
+            out[0][-1] += 1
+        else:
+            out[0] += [v, 1]
+    for s in range(1, settings):
+        runs = []
+        for i, (v, b) in enumerate(zip(idx[s * n:(s + 1) * n], base)):
+            if v != b and runs and runs[-3] + runs[-2] == i and runs[-1] == v:
+                runs[-2] += 1
+            elif v != b:
+                runs += [i, 1, v]
+        out.append(runs)
+    return out
+
+
+def unpack(packed):
+    base = [v for v, c in zip(packed[0][::2], packed[0][1::2]) for _ in range(c)]
+    out = list(base)
+    for runs in packed[1:]:
+        block = list(base)
+        for i, c, v in zip(runs[::3], runs[1::3], runs[2::3]):
+            block[i:i + c] = [v] * c
+        out += block
+    return out
+
+
+def loads(text):
+    t = json.loads(text)
+    t["attn"] = unpack(t["attn"])
+    return t
 
 
 def dumps(t):
     enc = lambda v: json.dumps(v, separators=(",", ":"))
     return ('{"key":%s,\n"plans":[\n%s\n],\n"gemm":%s,\n"attn":%s}\n'
-            % (enc(t["key"]), ",\n".join(enc(p) for p in t["plans"]), enc(t["gemm"]), enc(t["attn"])))
+            % (enc(t["key"]), ",\n".join(enc(p) for p in t["plans"]), enc(t["gemm"]), enc(pack(t["attn"], len(ATTN_SETTINGS)))))
 
 
 if __name__ == "__main__":
-    text = dumps(table())
+    keep = None
+    if os.path.exists(OUT):
+        with open(OUT) as f:
+            keep = loads(f.read())
+    text = dumps(table(keep))
     if "--stdout" in sys.argv:
         sys.stdout.write(text)
     else:
