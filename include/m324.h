@@ -43,7 +43,8 @@ typedef enum { M324_AUX_NONE = 0, M324_AUX_STORE_PREACT = 1, M324_AUX_MUL_GELU_G
  *   epilogue and only partial sums leave, aux = float part[N / 64][M][3] (C may be NULL); m324_n3_finish adds the N / 64
  *   column blocks in a fixed order and the last layer's bias.  N % 256 == 0, K % 64 == 0, K >= 128.                       */
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change).  m324_gemm_rows and m324_attention_rows were ADDED at version 23
+ * without a bump: no existing prototype or struct changed, and the project's test suite pins the number. */
 int m324_abi_version(void);
 /* Copies the calling thread's last error text into buf (NUL-terminated); returns its length. */
 int m324_last_error(char* buf, int n);
@@ -123,6 +124,15 @@ int m324_gemm(const m324_gemm_args* a, void* stream);
  * q projection of the mesh points and k|v projection of the latent tokens (transformer.py:112-132 under Pcd_motion.py:556-560).
  * Any other pair returns M324_ERR_UNSUPPORTED without launching anything: issue two m324_gemm calls. */
 int m324_gemm_pair(const m324_gemm_args* a, const m324_gemm_args* b, void* stream);
+/* m324_gemm with a row map on the INPUT side: row m of A and of `residual` is read from source row
+ * (m / in_gin) * in_gout + m % in_gin + in_off (out_row's arithmetic; in_gin > 0, in_off + in_gin <= in_gout, M % in_gin == 0);
+ * C, ln_stats_out and ln_copy_out are indexed by m.  The trunk's last per-frame block continues on the 64 latent rows of every
+ * frame only (the decoder reads nothing else, Pcd_motion.py:520): its out-projection gathers them from the attention output and
+ * from the stream and writes a compact stream with its statistics and twin -- no gather copy.  Built for exactly that: bf16 A,
+ * fp32 residual that is not C, fp32 C, LayerNorm-fold producer (ln_stats_out + ln_copy_out), no row_gin / res_rows / aux, always
+ * on the 128 x 128 chunk ring; a row's result is m324_gemm's on the gathered rows bit for bit.  Anything else returns
+ * M324_ERR_UNSUPPORTED without launching. */
+int m324_gemm_rows(const m324_gemm_args* a, int in_gin, int in_gout, int in_off, void* stream);
 /* Host-only: writes the kernel symbol (as rocprofv3 prints the template) and its grid in threads that m324_gemm would
  * launch for `a` into buf; returns the schedule number.  bench.py labels its per-launch HIP-event rows with it so that
  * they can be matched against the committed rocprofv3 summaries (profiles/). */
@@ -235,6 +245,14 @@ int m324_qkv_split(const void* q_src, long ldq, const void* k_src, long ldk, con
 enum { M324_ATTN_Q_PRESCALED = 1, M324_ATTN_V_ROWMAJOR = 2, M324_ATTN_SCORES_BOUNDED = 4 };
 int m324_attention(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo,
                    int B, int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, void* stream);
+/* The same for the first q_rows queries of every (batch, head) only: Lq keeps its meaning for strides, output rows
+ * (O[(b * Lq + q) * ldo + h * 64]) and the kernel's 32-row query blocks; rows >= q_rows of O (and lse) are not written.
+ * q_rows % 32 == 0 (or q_rows >= Lq, the whole problem): the kernel moves its softmax reference maximum on a vote over a 32-row
+ * block, so whole blocks of the full call -- and only those -- come out bit-identical to it.  The launch is m324_attention's
+ * kernel (see m324_attention_plan) on ceil(q_rows / rows per workgroup) query tiles.  Kernels without the window (the fp32 kernel,
+ * the long-sequence streams, the shared-query frame-pair kernel) return M324_ERR_UNSUPPORTED without launching. */
+int m324_attention_rows(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo,
+                        int B, int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, int q_rows, void* stream);
 /* Host-only twin of m324_gemm_plan for m324_attention (flags = the q_prescaled flag word; | 256: q_bstride == 0, one query
  * set shared by every batch, which the plan cannot see otherwise). */
 int m324_attention_plan(int B, int H, int Lq, int Lk, int flags, int dtype, char* buf, int n);

@@ -44,6 +44,7 @@ BF16_DECODER_STREAM = switches.flag("M324_BF16_DECODER")    # the decoder's resi
 HOIST_DECODER_Q = switches.flag("M324_HOIST_Q")             # hoisted decoder q projection (graph capture)
 _PATH_ROWS = 64           # at most this many rows: the bf16 kernels' small-problem paths (decode-only chunk plans stay off the line)
 DECODE_ROWS = int(switches.get("M324_DECODE_ROWS"))         # max (frames x points) rows per decoder pass: bounds the [rows, 4C] MLP buffer
+LAST_BLOCK_ROWS = switches.flag("M324_LAST_BLOCK_ROWS")    # the trunk's last per-frame block continues on the latent rows only
 MXFP8_DEFAULT = switches.flag("M324_MXFP8")                # inference_precision of a model whose config names none: "mxfp8" (1) / "bf16"
 
 
@@ -856,24 +857,40 @@ class Motion_Latent_Model(nn.Module):
             if "trunk.qkv" not in mx.roles:            # an MX q|k|v projection normalises the stream itself
                 fold.from_stream(tok, self.global_transformer_blocks[0].norm1.eps)
         n_pairs = len(self.global_transformer_blocks)
+        # Behind the last per-frame block the stream has two readers, the decoder's k|v projection and the motion latent, and both
+        # read rows 4 .. 4 + K of every frame: that block's attention queries, out-projection and MLP run on those rows only
+        # (QK_Norm_TransformerBlock.run rows_out) and leave a compact stream [B*T*K, C].  Stage captures, the frame-parallel forward,
+        # training steps, the fp32 mode and an MX MLP keep the whole stream.
+        lat_rows = (LAST_BLOCK_ROWS and cap is None and shard is None and fold is not None and n_pairs > 0 and Lt < 2048
+                    and _transformer.rows_window(K, 4) <= Lt and _transformer.fuse_qkv(P, B * T * Lt, Lt)
+                    and LNFold.usable(P, B * T * K, C))
+        tok_lat = None
         for i, (gblk, lblk) in enumerate(zip(self.global_transformer_blocks, self.local_transformer_blocks)):
             with mx:
                 gblk.run(P, tok, B, T * Lt, kv_gather=kv_gather, fold=fold)
-                lblk.run(P, tok, B * T, Lt, fold=fold, feed_next=i + 1 < n_pairs)     # the decoder gathers its own rows
+                if lat_rows and i + 1 == n_pairs:
+                    tok_lat = lblk.run(P, tok, B * T, Lt, fold=fold, feed_next=False, rows_out=(K, Lt, 4))
+                else:
+                    lblk.run(P, tok, B * T, Lt, fold=fold, feed_next=i + 1 < n_pairs)     # the decoder gathers its own rows
             if cap is not None and "trunk_block0" not in cap:
                 cap["trunk_block0"] = tok.clone()
         if cap is not None:
             cap["trunk_out"] = tok.clone()
 
         latent = None
-        if keep_latent:
+        if keep_latent and tok_lat is not None:
+            latent = tok_lat.view(B, T, K, C)                # the compact stream IS the latent
+        elif keep_latent:
             # rows 4..4+K of every frame, compact: ONE strided row copy (m324_cast fp32 -> fp32 over [B*T, Lt*C] rows)
             latent = torch.empty((B * T, K * C), dtype=torch.float32, device=dev)
             ops.cast(tok.view(B * T, Lt * C)[:, 4 * C:(4 + K) * C], torch.float32, out=latent)
             latent = latent.view(B, T, K, C)
         if encode_only:
             return edict(input_data=sample, latent=latent)
-        out = self._decode(P, sample, tok, (K, Lt, 4), B, T, hoisted, cap)
+        if tok_lat is not None:
+            out = self._decode(P, sample, tok_lat, (0, 0, 0), B, T, hoisted, cap)     # identity map, as a handed-in latent's
+        else:
+            out = self._decode(P, sample, tok, (K, Lt, 4), B, T, hoisted, cap)
 
         if shard is not None and parallel.collectives_on(shard[1]):
             rank, world, group = shard[:3]

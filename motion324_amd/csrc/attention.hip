@@ -99,7 +99,9 @@ template <bool PRESCALED, int NQ, int NWV, bool VROW = false, int NST = 3>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 || NST == 2) ? 4 : 1)) void attn_bf16_kernel(const bf16_t* __restrict__ Q, long q_bstride,
                                                         const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
                                                         bf16_t* __restrict__ O, long ldo, int H, int Lq, int Lk,
-                                                        int Lkp, float scale_log2e, float* __restrict__ lse, int nqt) {
+                                                        int Lkp, float scale_log2e, float* __restrict__ lse, int nqt, int q_rows) {
+    // q_rows (m324_attention_rows): only queries [0, q_rows) of every (batch, head) are computed and stored; Lq keeps the strides
+    // and the 32-row block structure, so a computed block is the block the full launch (q_rows = Lq) computes.
     // [stage][K | Vt]; the one-tile form appends a wave-private 4-KiB block per wave for the whole-row output stores (its only
     // stage is still being read by the slower waves when the first one is done; 32 KiB keeps four workgroups per CU)
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * ASTAGE + (NST == 1 ? NWV * 4096 : 0)];
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
         const int q = q0 + n * QW + l31;
-        const bool ok = q < Lq;
+        const bool ok = q < q_rows;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             uint4 v = ok ? *reinterpret_cast<const uint4*>(Qh + (long)q * 64 + ks * 16 + hi * 8) : make_uint4(0, 0, 0, 0);
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
     // Partly filled last query tile (per-frame blocks: L = 257 -> its third 128-row tile holds ONE row, L = 324 -> 68): the waves
     // whose 32 rows lie past Lq only stage tiles and meet the barriers.  The guard lives in a second copy of the loop that only
     // those workgroups run (round 2 put the branch into the one loop every workgroup runs: +4 % on the whole kernel).
-    const bool idle = q0 >= Lq;
+    const bool idle = q0 >= q_rows;
     auto tiles = [&](auto guard_tag) {
         constexpr bool GUARD = decltype(guard_tag)::value;
         for (int t = 0; t < nt; ++t) {
@@ -347,7 +349,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
 
         }
     };
-    if (NWV == 4 && NQ == 1 && NST == 3 && (qt + 1) * NWV * QW > Lq) tiles(std::true_type{});
+    if (NWV == 4 && NQ == 1 && NST == 3 && (qt + 1) * NWV * QW > q_rows) tiles(std::true_type{});
     else tiles(std::false_type{});
 
     // ---- normalise and store.  o[n][db][r]: d = db*32 + (r&3) + 8*(r>>2) + 4*hi, q = l31
@@ -356,7 +358,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
         const float l_tot = l_run[n] + __shfl_xor(l_run[n], 32, 64);
         const float inv = 1.0f / l_tot;
         const int q = q0 + n * QW + l31;
-        if (lse && q < Lq && hi == 0) lse[((long)b * H + h) * Lq + q] = m_ref[n] + log2f(l_tot);   // log2-domain LSE
+        if (lse && q < q_rows && hi == 0) lse[((long)b * H + h) * Lq + q] = m_ref[n] + log2f(l_tot);   // log2-domain LSE
         // The two lanes of a query (l, l + 32) hold alternating 4-value groups of its row.  v_permlane32_swap trades the
         // odd groups of the lower lanes for the even groups of the upper ones, so every lane has whole 8-value (16-byte)
         // chunks; those bounce through a wave-private, XOR-swizzled 32 x 128-byte LDS block so that a store instruction
@@ -389,7 +391,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 8 ? (VROW ? 2 : 4) : ((NST == 1 ||
         for (int p = 0; p < 4; ++p) {
             const int r = p * 8 + r8;
             const uint4 v = *reinterpret_cast<const uint4*>(scr + r * 128 + ((c8 ^ (r & 7)) << 4));
-            if (q0 + n * QW + r < Lq) *reinterpret_cast<uint4*>(obase + (long)r * ldo) = v;
+            if (q0 + n * QW + r < q_rows) *reinterpret_cast<uint4*>(obase + (long)r * ldo) = v;
         }
     }
 }
@@ -1133,8 +1135,9 @@ static AttnPlan attn_plan(int B, int H, int Lq, int Lk, int flags, int dtype) {
 
 static constexpr int attn_key(bool ps, int nw, bool vrow, int nst) { return (int)ps | nw << 1 | (int)vrow << 5 | nst << 6; }
 
-extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B,
-                              int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, void* stream) {
+// m324_attention (q_rows = Lq) and m324_attention_rows (the first q_rows queries of every (batch, head)) are one launch path
+static int attention_launch(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B, int H, int Lq,
+                            int Lk, float scale, int q_prescaled, float* lse, int dtype, int q_rows, void* stream) {
     M324_REQUIRE(Q && K && Vt && O, "m324_attention: null pointer");
     M324_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, "m324_attention: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
     M324_REQUIRE(ldo >= (long)H * 64, "m324_attention: ldo too small");
@@ -1145,12 +1148,22 @@ extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, cons
     const int Lkp = (Lk + 63) / 64 * 64;
     hipStream_t s = (hipStream_t)stream;
     const float sl = (q_prescaled & M324_ATTN_Q_PRESCALED) ? 1.0f : scale * LOG2E;
-    const AttnPlan p = attn_plan(B, H, Lq, Lk, (q_prescaled & 7) | (q_bstride == 0 ? 256 : 0), dtype);
+    AttnPlan p = attn_plan(B, H, Lq, Lk, (q_prescaled & 7) | (q_bstride == 0 ? 256 : 0), dtype);
+    if (q_rows < Lq) {
+        // the window is a run-time argument of attn_bf16_kernel: the full launch's kernel on fewer query tiles, in the full launch's
+        // grid form (flat or 3-D); the other families compute every row
+        if (p.family != ATTN_BF16)
+            M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention_rows: the kernel of this shape (B=%d H=%d Lq=%d Lk=%d dtype=%d) takes no query window",
+                      B, H, Lq, Lk, dtype);
+        const int tiles = ceil_div(q_rows, p.nw * QW);
+        if (p.nqt > 0) p.nqt = tiles, p.grid = dim3((unsigned)tiles * H * B, 1, 1);
+        else p.grid.x = (unsigned)tiles;
+    }
 #define M324_ATTN(PS, NWV, VROW, NST)                                                                                   \
     case attn_key(PS, NWV, VROW, NST):                                                                                  \
         hipLaunchKernelGGL((attn_bf16_kernel<PS, 1, NWV, VROW, NST>), p.grid, dim3(p.threads), 0, s,                    \
                            (const bf16_t*)Q, q_bstride, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)O, ldo, H, Lq, Lk, \
-                           Lkp, sl, lse, p.nqt);                                                                         \
+                           Lkp, sl, lse, p.nqt, q_rows);                                                                 \
         break
     switch (p.family) {
         case ATTN_F32:
@@ -1183,6 +1196,24 @@ extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, cons
 #undef M324_ATTN
     M324_CHECK_LAUNCH("m324_attention");
     return M324_OK;
+}
+
+extern "C" int m324_attention(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B,
+                              int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, void* stream) {
+    return attention_launch(Q, q_bstride, K, Vt, O, ldo, B, H, Lq, Lk, scale, q_prescaled, lse, dtype, Lq, stream);
+}
+
+// The first q_rows queries of every (batch, head); rows >= q_rows of O (and of lse) are not written.  q_rows is a multiple of 32 (or
+// >= Lq, the whole problem): the lazy softmax maximum moves on a vote of a wave's 32-row block, so only whole blocks of the full
+// launch reproduce its bits.
+extern "C" int m324_attention_rows(const void* Q, long q_bstride, const void* K, const void* Vt, void* O, long ldo, int B,
+                                   int H, int Lq, int Lk, float scale, int q_prescaled, float* lse, int dtype, int q_rows,
+                                   void* stream) {
+    M324_REQUIRE(q_rows > 0, "m324_attention_rows: q_rows=%d", q_rows);
+    if (Lq > 0 && q_rows < Lq && q_rows % 32 != 0)
+        M324_FAIL(M324_ERR_UNSUPPORTED, "m324_attention_rows: q_rows=%d below Lq=%d must be a multiple of 32 (whole query blocks)", q_rows, Lq);
+    return attention_launch(Q, q_bstride, K, Vt, O, ldo, B, H, Lq, Lk, scale, q_prescaled, lse, dtype,
+                            Lq > 0 && q_rows > Lq ? Lq : q_rows, stream);
 }
 
 // Name and grid (threads) of the kernel m324_attention would launch: see m324_gemm_plan.  flags: attn_plan.  Returns 0 for the fp32

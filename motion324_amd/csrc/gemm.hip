@@ -511,9 +511,12 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(const bf16_t* __restr
 constexpr int CHUNK13 = 128 * ROWB;               // 16 KiB
 
 // (the body of one workgroup = one tile; gemm_ring2_kernel runs it on its own grid, gemm_ring2_pair_kernel on one of two problems)
-template <typename TOUT, int ACT, int RES>
+// GATHER (gemm_ring2_rows_kernel): the rows of A and of the residual are read through `im` (gemm_tile.h InRows) -- per-lane offset
+// arithmetic in front of the ring and in the residual prefetch; C, the statistics and the twin stay compact.
+template <typename TOUT, int ACT, int RES, bool GATHER = false>
 __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ W, long ldw, TOUT* C, long ldc,
-                                           int M, int N, int K, const Epilogue& ep, int ntn, int xcd_remap, int tile, int ntiles) {
+                                           int M, int N, int K, const Epilogue& ep, int ntn, int xcd_remap, int tile, int ntiles,
+                                           const InRows im = InRows{0, 0, 0}) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[5 * CHUNK13];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -529,10 +532,12 @@ __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long ld
     for (int i = 0; i < 4; ++i) {
         const int r = (wave * 4 + i) * 8 + (lane >> 3);
         const int c = ((lane & 7) ^ ((r >> 1) & 7)) * 8;
-        ga[i] = (unsigned)(((long)min(r, M - 1 - m0) * lda + c) * 2);
+        // (GATHER: the map is monotonic, so the offsets from the tile's first source row are non-negative; host: they fit 31 bits)
+        const long ar = GATHER ? im.row(m0 + min(r, M - 1 - m0)) - im.row(m0) : (long)min(r, M - 1 - m0);
+        ga[i] = (unsigned)((ar * lda + c) * 2);
         gb[i] = (unsigned)(((long)min(r, N - 1 - n0) * ldw + c) * 2);
     }
-    const __amdgpu_buffer_rsrc_t ra = dma_rsrc(A + (long)m0 * lda), rb = dma_rsrc(W + (long)n0 * ldw);
+    const __amdgpu_buffer_rsrc_t ra = dma_rsrc(A + (GATHER ? im.row(m0) : (long)m0) * lda), rb = dma_rsrc(W + (long)n0 * ldw);
     const __amdgpu_buffer_rsrc_t rnone = dma_rsrc_none(A);    // look-ahead pieces past the end of K: gemm_tile.h dma_rsrc_none
     auto issue2 = [&](const unsigned (&g)[4], int i0, int st, int pos, bool live = true) {
         unsigned char* d = smem + pos * CHUNK13 + wave * 4096 + i0 * 1024;
@@ -582,7 +587,7 @@ __device__ __forceinline__ void ring2_tile(const bf16_t* __restrict__ A, long ld
     ResPre<2> pres;
     const bool use_pres = PRE_RES && ep.residual != nullptr;
     if constexpr (PRE_RES) {
-        if (use_pres) res_prefetch<2>(ep, M, N, m0 + wm * 64, n0 + wn * 64, lane, pres);
+        if (use_pres) res_prefetch<2, GATHER>(ep, M, N, m0 + wm * 64, n0 + wn * 64, lane, pres, im);
     }
     LnPreT<2> ln_pre;
     ln_prefetch<ACT, 2>(ep, M, N, m0 + wm * 64, n0 + wn * 64, lane, ln_pre);
@@ -641,6 +646,16 @@ __global__ __launch_bounds__(256, 2) void gemm_ring2_kernel(const bf16_t* __rest
                                                             long ldw, TOUT* C, long ldc, int M, int N, int K, Epilogue ep, int ntn,
                                                             int xcd_remap) {
     ring2_tile<TOUT, ACT, RES>(A, lda, W, ldw, C, ldc, M, N, K, ep, ntn, xcd_remap, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// m324_gemm_rows: the same tile with row-gathered A and residual.  Built for the fp32 residual update whose values are prefetched
+// in front of the ring (PRE_RES in ring2_tile: the epilogue then reads no residual row itself, so the map lives in two places).
+template <typename TOUT, int ACT, int RES>
+__global__ __launch_bounds__(256, 2) void gemm_ring2_rows_kernel(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ W,
+                                                                 long ldw, TOUT* C, long ldc, int M, int N, int K, Epilogue ep, int ntn,
+                                                                 int xcd_remap, InRows im) {
+    static_assert(RES == 1 && sizeof(TOUT) == 4, "the gathered residual is read by res_prefetch only");
+    ring2_tile<TOUT, ACT, RES, true>(A, lda, W, ldw, C, ldc, M, N, K, ep, ntn, xcd_remap, (int)blockIdx.x, (int)gridDim.x, im);
 }
 
 // Two independent problems in one launch (m324_gemm_pair: the decoder's q and k|v projections -- 96 and 192 tiles, each a 12-stage
@@ -1403,6 +1418,33 @@ extern "C" int m324_gemm(const m324_gemm_args* a, void* stream) {
     if (a->in_dtype == M324_BF16 && a->out_dtype == M324_F32) return launch<bf16_t, float>(a, s);
     if (a->in_dtype == M324_F32 && a->out_dtype == M324_F32) return launch<float, float>(a, s);
     M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: unsupported dtype pair in=%d out=%d", a->in_dtype, a->out_dtype);
+}
+
+// m324_gemm with a row map on the INPUT side: row m of A and of the residual is source row (m / in_gin) * in_gout + m % in_gin +
+// in_off; C, ln_stats_out and ln_copy_out are indexed by m.  Built for the trunk's last per-frame out-projection: bf16 A, an fp32
+// residual that is not C, fp32 C, LayerNorm-fold producer with its bf16 twin, always on the 128 x 128 chunk ring (schedule 13: the
+// schedule m324_gemm runs the same out-projection on).  Anything else: M324_ERR_UNSUPPORTED, nothing launched.
+extern "C" int m324_gemm_rows(const m324_gemm_args* a, int in_gin, int in_gout, int in_off, void* stream) {
+    const int rc = gemm_validate(a);
+    if (rc != M324_OK) return rc;
+    M324_REQUIRE(in_gin > 0 && in_gout >= in_gin && in_off >= 0 && in_off + in_gin <= in_gout,
+                 "m324_gemm_rows: the map takes in_gin rows at in_off of every in_gout rows (in_gin=%d in_gout=%d in_off=%d)", in_gin, in_gout, in_off);
+    M324_REQUIRE(a->M % in_gin == 0, "m324_gemm_rows: M=%d is not a whole number of groups of %d rows", a->M, in_gin);
+    const GemmPlan p = make_plan(a);
+    const bool ring_ok = a->K % 64 == 0 && a->K >= 128;
+    if (!(a->in_dtype == M324_BF16 && a->out_dtype == M324_F32 && p.actx == 48 && p.res == 1 && p.nbatch == 1 && ring_ok && vec_ok(a) &&
+          (const void*)a->residual != (const void*)a->C))
+        M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm_rows: built for the fp32 LayerNorm-statistics producer (bf16 A, fp32 residual != C, fp32 C + "
+                  "bf16 twin) on the 128 x 128 chunk ring");
+    // a tile's 128 rows span at most 128 / in_gin + 2 groups: their byte offsets from the tile's first source row stay below 2 GiB
+    M324_REQUIRE(((long)(BM / in_gin + 2) * in_gout * a->lda + a->K) * 2 < 0x7FFFFFFFl, "m324_gemm_rows: row map too wide for the staging window");
+    const Epilogue ep = make_epilogue(a);
+    const long wg = (long)ceil_div(a->N, BN) * ceil_div(a->M, BM);
+    hipLaunchKernelGGL((gemm_ring2_rows_kernel<float, 48, 1>), dim3((unsigned)wg), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a->A,
+                       a->lda, (const bf16_t*)a->W, a->ldw, (float*)a->C, a->ldc, a->M, a->N, a->K, ep, ceil_div(a->N, BN), xcd_mode(a),
+                       InRows{in_gin, in_gout, in_off});
+    M324_CHECK_LAUNCH("m324_gemm_rows");
+    return M324_OK;
 }
 
 // Two GEMMs in ONE launch (horizontal fusion).  Built for the pair that needs it: two bf16 projections with the head-major q|k|v

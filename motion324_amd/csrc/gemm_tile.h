@@ -686,15 +686,23 @@ struct ResPre {
         return make_float4(v[4 * p], v[4 * p + 1], v[4 * p + 2], v[4 * p + 3]);
     }
 };
-template <int MI>
-__device__ __forceinline__ void res_prefetch(const Epilogue& ep, int M, int N, int mw, int nw, int lane, ResPre<MI>& pr) {
+// Row map of m324_gemm_rows: GEMM row m reads row (m / gin) * gout + m % gin + off of A and of the residual (out_row's arithmetic on
+// the input side: the latent rows of every frame of a token stream, without a gather copy).
+struct InRows {
+    int gin, gout, off;
+    __device__ __forceinline__ long row(int m) const { return (long)(m / gin) * gout + (m % gin) + off; }
+};
+template <int MI, bool GATHER = false>
+__device__ __forceinline__ void res_prefetch(const Epilogue& ep, int M, int N, int mw, int nw, int lane, ResPre<MI>& pr,
+                                             const InRows im = InRows{0, 0, 0}) {
     static_assert(MI <= 4, "ResPre holds four row blocks");
     const int rr = lane >> 4, ncl = min(nw + (lane & 15) * 4, N - 4);
     auto block = [&](int i) {
         res_f32x32 v;
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
-            const float4 x = *reinterpret_cast<const float4*>(ep.residual + (long)min(mw + i * 32 + rr + 4 * p, M - 1) * ep.ldr + ncl);
+            const int mr = min(mw + i * 32 + rr + 4 * p, M - 1);
+            const float4 x = *reinterpret_cast<const float4*>(ep.residual + (GATHER ? im.row(mr) : (long)mr) * ep.ldr + ncl);
             v[4 * p] = x.x, v[4 * p + 1] = x.y, v[4 * p + 2] = x.z, v[4 * p + 3] = x.w;
         }
         return v;

@@ -67,6 +67,7 @@ SIGNATURES = {
     "m324_gemm": [C.POINTER(GemmArgs), _P],
     "m324_gemm_plan": [C.POINTER(GemmArgs), C.c_char_p, _I],
     "m324_gemm_pair": [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _P],
+    "m324_gemm_rows": [C.POINTER(GemmArgs), _I, _I, _I, _P],
     "m324_mx_quant": [_P, _I, _L, _I, _I, _P, _L, _P, _L, _P],
     "m324_layernorm_mx": [_P, _L, _P, _P, _F, _I, _I, _P, _L, _P, _L, _P],
     "m324_gemm_mx": [C.POINTER(GemmArgs), _P, _L, _P, _L, _P, _L, _P],
@@ -80,6 +81,7 @@ SIGNATURES = {
     "m324_layernorm_pair": [_P, _L, _P, _P, _F, _P, _L, _I, _I, _I, _I, _P, _L, _P, _P, _F, _P, _L, _I, _I, _I, _I, _I, _I, _P],
     "m324_qkv_split": [_P, _L, _P, _L, _P, _L, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "m324_attention": [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _F, _I, _P, _I, _P],
+    "m324_attention_rows": [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _F, _I, _P, _I, _I, _P],
     "m324_attention_merge": [_P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_patchify": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P],
     "m324_patchify_u8": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _P],

@@ -175,8 +175,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
          preact_out: Optional[torch.Tensor] = None, gelu_grad_of: Optional[torch.Tensor] = None,
          gelu_grad_out: Optional[torch.Tensor] = None, mul_by: Optional[torch.Tensor] = None,
          qkv_heads: Optional[tuple] = None, n3: Optional[tuple] = None, ln: Optional[tuple] = None,
-         stats_out: Optional[torch.Tensor] = None, copy_out: Optional[torch.Tensor] = None, defer: Optional[list] = None) -> torch.Tensor:
+         stats_out: Optional[torch.Tensor] = None, copy_out: Optional[torch.Tensor] = None, defer: Optional[list] = None,
+         in_rows: Optional[tuple] = None) -> torch.Tensor:
     """out[row_map(m), :N] = epilogue(a[M,K] @ w[N,K]^T); see include/m324.h m324_gemm.
+    in_rows = (gin, gout, off) (m324_gemm_rows): M = out.shape[0], and row m reads row (m // gin) * gout + m % gin + off of `a` and
+    of `residual`; out, stats_out and copy_out are compact.  Built for the fp32 LayerNorm-statistics producer only.
     preact_out [M, N] (out's dtype) also receives the value the activation is applied to (M324_AUX_STORE_PREACT);
     gelu_grad_of [M, N] = z: the result is multiplied by gelu'(z) (M324_AUX_MUL_GELU_GRAD).  Training only.
     gelu_grad_out [M, N] receives gelu'(pre-activation) (M324_AUX_STORE_GELU_GRAD) and mul_by [M, N] multiplies the result
@@ -194,6 +197,14 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
     N = w.shape[0]
     if w.shape[1] != K or a.dtype != w.dtype:
         raise L.M324Error(f"gemm: a{tuple(a.shape)} {a.dtype} vs w{tuple(w.shape)} {w.dtype}")
+    if in_rows is not None:
+        gin_i, gout_i, off_i = (int(v) for v in in_rows)
+        M = out.shape[0] if out is not None else 0
+        src_need = ((M - 1) // gin_i * gout_i + (M - 1) % gin_i + off_i + 1) if gin_i > 0 and M > 0 else 0
+        if (gin_i <= 0 or M <= 0 or qkv_heads is not None or n3 is not None or residual is None or a.shape[0] < src_need
+                or residual.shape[0] < src_need or residual.data_ptr() == out.data_ptr()):
+            raise L.M324Error(f"gemm: in_rows {tuple(in_rows)} needs an output of M rows, a and a residual (not the output) of "
+                              f"{src_need} rows: a{tuple(a.shape)}")
     args = L.GemmArgs()
     args.A, args.lda = _rows(a, "a")
     args.W, args.ldw = _rows(w, "w")
@@ -301,8 +312,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
         nbytes += residual.element_size() * N * (res_rows if 0 < res_rows < M else M)
     if copy_out is not None:
         nbytes += 2 * M * N
-    with span(f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * K, nbytes, tag):
-        L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
+    with span(f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * K, nbytes, tag + (f" in_rows={tuple(in_rows)}" if tag and in_rows else "")):
+        if in_rows is not None:
+            L.check(L.load().m324_gemm_rows(C.byref(args), gin_i, gout_i, off_i, _stream()), "m324_gemm_rows")
+        else:
+            L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
     return out
 
 
@@ -548,10 +562,12 @@ def qkv_split(q_src, k_src, v_src, q_w, k_w, eps: float, B: int, Lq: int, H: int
 
 def attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, out: torch.Tensor, *, shared_q: bool = False,
               scale: Optional[float] = None, prescaled: bool = False, lse: Optional[torch.Tensor] = None,
-              v_rowmajor: bool = False, bounded: bool = False) -> torch.Tensor:
+              v_rowmajor: bool = False, bounded: bool = False, q_rows: Optional[int] = None) -> torch.Tensor:
     """out[B*Lq, H*64] = softmax(Q K^T scale) V.  Q[Bq,H,Lq,64] (Bq == 1 with shared_q), K[B,H,Lk,64],
     Vt[B,H,64,Lkp] -- or, with v_rowmajor (bf16 only), V[B,H,Lk,64].  prescaled: Q carries Q_PRESCALE.
-    bounded: the caller vouches for |log2-domain score| <= 64 (M324_ATTN_SCORES_BOUNDED; see qk_score_bound)."""
+    bounded: the caller vouches for |log2-domain score| <= 64 (M324_ATTN_SCORES_BOUNDED; see qk_score_bound).
+    q_rows (m324_attention_rows): only the first q_rows queries of every (batch, head) are computed; the other rows of `out` are
+    not written.  A multiple of 32, and the written rows are the full call's bit for bit."""
     B, H, Lk, D = K.shape
     Lq = Q.shape[2]
     vshape = (B, H, Lk, 64) if v_rowmajor else (B, H, 64, (Lk + 63) // 64 * 64)
@@ -570,6 +586,15 @@ def attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, out: torch.Ten
     scale = 64 ** -0.5 if scale is None else scale
     esz = Q.element_size()
     flags = int(prescaled) | (2 if v_rowmajor else 0) | (4 if bounded else 0)       # M324_ATTN_*; the plan query takes shared_q as bit 8
+    if q_rows is not None:
+        nq = min(int(q_rows), Lq)
+        with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * nq * Lk * 64,
+                  esz * 64.0 * H * ((1 if shared_q else B) * nq + 2 * B * Lk + B * nq),
+                  f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk} q_rows={q_rows}"
+                  if _timing() else ""):
+            L.check(L.load().m324_attention_rows(_p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale, flags, _p(lse), code_of(Q.dtype),
+                                                 int(q_rows), _stream()), "m324_attention_rows")
+        return out
     with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * Lq * Lk * 64,
               esz * 64.0 * H * ((1 if shared_q else B) * Lq + 2 * B * Lk + B * Lq),
               f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk}"

@@ -30,6 +30,7 @@ HOST: Dict[str, Tuple[str, str, str]] = {
     "M324_TRAIN_STORE": ("1", "training.TRAIN_STORE", "training: the forward keeps block internals while they fit half of the free HBM (0: always recompute, the reference's checkpoint policy)"),
     "M324_WEIGHT_MIRROR": ("1", "optim.WEIGHT_MIRROR", "training: FusedAdamW keeps bf16 row-major and transposed copies of every Linear weight in two flat buffers, rewritten by one m324_weight_mirror launch after each update (0: Prepared casts / m324_transpose per weight and step)"),
     "M324_DEFER_COLSUM": ("1", "ops.DEFER_COLSUM", "training: the sums of the weight gradients' split-K partials and of the norm-weight partials wait in a queue and leave in one m324_colsum_multi launch per block (0: one m324_colsum launch each, at once)"),
+    "M324_LAST_BLOCK_ROWS": ("1", "Pcd_motion.LAST_BLOCK_ROWS", "bf16 inference with the LayerNorm fold: the trunk's last per-frame block computes only what its readers read -- attention queries up to the latent rows' 32-row block (m324_attention_rows), out-projection gathered onto the 64 latent rows of every frame (m324_gemm_rows), MLP on that compact stream; bit-identical (0: the whole stream, as stage captures, the frame-parallel forward, training and fp32 always do)"),
     "M324_MXFP8": ("0", "Pcd_motion.MXFP8_DEFAULT", "1: a model whose config names no model.inference_precision uses \"mxfp8\" -- block-scaled e4m3 operands for the GEMM roles of transformer.MX_ROLES (the trunk and DINOv2 q|k|v projections) in a bf16 inference forward (DESIGN section 4)"),
     "M324_PRECISION": ("", "prepared.compute_dtype()", "force bf16 / fp32 (default: follow torch.autocast like the reference)"),
     "M324_LIB": ("", "lib.LIB_PATH", "path of an alternative libm324.so (lab builds)"),

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, switches
-from .lib import ACT_GELU
+from .lib import ACT_GELU, M324Error
 from .prepared import Prepared
 
 LN_EPS = 1e-5     # nn.LayerNorm default, reference transformer.py:345-346,357,400,411
@@ -313,6 +313,11 @@ def fuse_proj(P: Prepared, rows: int) -> bool:
     return FUSE_QKV and not _FUSE_OFF and P.dtype == torch.bfloat16 and rows > 64 and not torch.is_grad_enabled()
 
 
+def rows_window(n_per: int, first: int) -> int:
+    """Query rows the windowed attention computes for wanted rows first .. first + n_per: whole 32-row blocks (m324_attention_rows)."""
+    return (first + n_per + 31) // 32 * 32
+
+
 class QK_Norm_TransformerBlock(nn.Module):
     """Pre-norm self-attention block (reference transformer.py:379-423)."""
 
@@ -326,8 +331,16 @@ class QK_Norm_TransformerBlock(nn.Module):
         self.mlp = MLP(dim, mlp_ratio=mlp_ratio, bias=mlp_bias, dropout=mlp_dropout)
 
     def run(self, P: Prepared, x: torch.Tensor, B: int, L: int, kv_gather=None, fold: Optional[LNFold] = None,
-            feed_next: bool = True) -> torch.Tensor:
+            feed_next: bool = True, rows_out: Optional[tuple] = None) -> torch.Tensor:
         """x: fp32 [B*L, C] residual stream, updated in place (x + attn(LN x); x + mlp(LN x)).
+
+        rows_out = (n_per, stride, first) (the trunk's last per-frame block; fused per-frame path with the fold only): everything
+        behind this block reads rows first .. first + n_per of every `stride` rows (the decoder: the latent tokens of every frame),
+        and in a per-frame block the other rows matter to nobody once the attention has read their K and V.  The q|k|v projection
+        runs as always; the attention computes the query rows up to the 32-row block that holds the last wanted row, the
+        out-projection gathers the wanted rows (attention output and residual) into a NEW compact stream [B * n_per, C] with its own
+        LNFold, and the MLP runs on that.  x is left without this block's update; the compact stream is returned: its rows are
+        the rows the full block would have written, bit for bit (kernels work row by row, the attention by whole 32-row blocks).
 
         kv_gather (frame-parallel global attention): object with start(kv_local [B*L, 2C]) / finish() -> (all ranks'
         [B*L_full, 2C], L_full) -- Pcd_motion._KVGather; queries stay local, keys/values cover the whole clip.  The k|v
@@ -366,9 +379,19 @@ class QK_Norm_TransformerBlock(nn.Module):
             V = torch.empty((B, a.num_heads, 64, L) if long_seq else (B, a.num_heads, L, 64), dtype=P.dtype, device=x.device)
             proj(src, w, None, bias=bias, qkv_heads=(Q, K, V, qw, kw, RMS_EPS, ops.Q_PRESCALE, L, a.num_heads),
                  **lnk(0, 3 * C))
+            if rows_out is not None:
+                n_per, stride, first = rows_out
+                assert fold is not None and not long_seq and stride == L and first + n_per <= L
+                ops.attention(Q, K, V, h, prescaled=True, v_rowmajor=True, q_rows=rows_window(n_per, first))
+                xl = torch.empty((B * n_per, C), dtype=torch.float32, device=x.device)
+                fl = LNFold(xl)
+                ops.gemm(h, P.mat(a.fc.weight), xl, bias=P.vec(a.fc.bias), residual=x, in_rows=(n_per, stride, first), **fl.producer())
+                return _mlp_residual(P, self.norm2, self.mlp, xl, fl, feed_next=False)
             ops.attention(Q, K, V, h, prescaled=True, v_rowmajor=not long_seq, bounded=long_seq and a.scores_bounded(P))
             ops.gemm(h, P.mat(a.fc.weight), x, bias=P.vec(a.fc.bias), residual=x, **out_kw())
             return _mlp_residual(P, self.norm2, self.mlp, x, fold, feed_next, mx=mlp_mx)
+        if rows_out is not None:
+            raise M324Error("rows_out: the fused per-frame path only (fuse_qkv, no kv_gather)")
         if kv_gather is None:
             qkv = torch.empty((rows, 3 * C), dtype=P.dtype, device=x.device)
             proj(src, w, qkv, bias=bias, **lnk(0, 3 * C))

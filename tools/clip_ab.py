@@ -29,7 +29,8 @@ sample = {k: torch.from_numpy(v).to(dev) for k, v in s.items()}
 HOST = {"M324_ATTN_BOUNDED": ("motion324_amd.transformer", "ATTN_BOUNDED"), "M324_FOLD_LN": ("motion324_amd.transformer", "FOLD_LN"),
         "M324_FOLD_MERGE": ("motion324_amd.transformer", "FOLD_MERGE"),
         "M324_BF16_DECODER": ("motion324_amd.Pcd_motion", "BF16_DECODER_STREAM"), "M324_FUSE_HEAD": ("motion324_amd.Pcd_motion", "FUSE_HEAD_N3"),
-        "M324_OVERLAP": ("motion324_amd.Pcd_motion", "OVERLAP_SHAPE_ENCODER"), "M324_HOIST_Q": ("motion324_amd.Pcd_motion", "HOIST_DECODER_Q")}
+        "M324_OVERLAP": ("motion324_amd.Pcd_motion", "OVERLAP_SHAPE_ENCODER"), "M324_HOIST_Q": ("motion324_amd.Pcd_motion", "HOIST_DECODER_Q"),
+        "M324_LAST_BLOCK_ROWS": ("motion324_amd.Pcd_motion", "LAST_BLOCK_ROWS")}
 
 
 BOTH = {"M324_HP": ("motion324_amd.transformer", "HP")}          # library switches the host mirrors
