@@ -104,8 +104,8 @@ class GraphedForward:
         # max_graphs > 0: keep at most that many captured shape sets, dropping the least recently used (each graph owns a
         # private memory pool with a clip's activations and its static inputs).  capture_error_mode: torch.cuda.graph's
         # -- "thread_local" lets other threads (a DataLoader's pin-memory thread, another stream's allocation) keep
-        # calling into HIP while this thread captures.  One override: a segmented capture with M324_KV_OVERLAP=1 (an
-        # exchange in flight across a cut) turns "global" into "thread_local" (see __call__).
+        # calling into HIP while this thread captures.  One override: a segmented capture (the transport's
+        # threads poll the exchange behind every cut) turns "global" into "thread_local" (see __call__).
         # weak: the model itself owns this object (Motion_Latent_Model's automatic graph replay) -- a strong reference back
         # would make model <-> graphs cyclic garbage, which Python's collector may free at any time, e.g. in the middle
         # of a LATER stream capture, where destroying a hipGraph aborts the process
@@ -169,13 +169,15 @@ class GraphedForward:
                 try:
                     if self.segmented:
                         global _SEGMENTER
-                        # With M324_KV_OVERLAP=1 an exchange is IN FLIGHT while the next link of the chain is being captured, and the
-                        # transport's own threads (gloo's copies through host memory; RCCL's watchdog) keep calling into HIP -- in
-                        # "global" mode any such call invalidates the capture on this thread, so THAT form (and only that form)
-                        # captures "thread_local" whatever the caller asked for.  Without the overlap the caller's mode stands.
-                        from . import Pcd_motion
+                        # Every link behind the first is opened right behind an eager exchange (_Segmenter.cut), and the transport's
+                        # own threads keep calling into HIP on its account: gloo copies through host memory, and RCCL's watchdog
+                        # polls the exchange's event (hipEventQuery) until one of its 100-ms rounds has seen it complete -- with
+                        # M324_KV_OVERLAP=1 because the exchange is still in flight, without it because the watchdog has not
+                        # looked yet.  In "global" mode such a call fails with hipErrorStreamCaptureUnsupported: it invalidates
+                        # the capture on this thread and the watchdog's exception ends the process (seen in the 1-rank RCCL test).
+                        # So a chain captures "thread_local" where the caller asked for "global".
                         mode = self.capture_error_mode
-                        if Pcd_motion.KV_OVERLAP and mode == "global":
+                        if mode == "global":
                             mode = "thread_local"
                         g = _Segmenter(mode)
                         cap_stream = torch.cuda.Stream()
