@@ -357,6 +357,43 @@ int m324_smooth_oneeuro(const float* trajs, float* out, int B, int T, int N, flo
  * (scripts/inference_with_video_mesh.py:112-115, a scipy cKDTree query in the reference).  query [n_query,3], ref [n_ref,3]. */
 int m324_nearest_point(const float* query, int n_query, const float* ref, int n_ref, int* index, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Geometry evaluation (csrc/geometry.hip; added at ABI 23 without a bump, like m324_gemm_rows): what motion324_amd/evaluation.py
+ * runs on the device.  replaces: the cKDTree queries and numpy reductions of evaluation/evaluation_pcd.py (icp_alignment :205-408,
+ * compute_chamfer_distance :575-588, compute_fscore :591-609).  No kernel here uses atomics; every result is independent of the
+ * grid, the slice count and the arrival order.
+ *
+ * m324_nn_search: batched brute-force nearest neighbour.  Per batch item b: query + b * stride_q is [n_query, 3] fp32,
+ *   ref + b * stride_r is [n_ref, 3] fp32 (strides in ELEMENTS; 0 = the same set for every item).
+ *   dist [batch, n_query] fp32 (Euclidean, sqrt of the winning d2) and index [batch, n_query] int32; either may be NULL, not both.
+ *   d2 = dx*dx + dy*dy + dz*dz in fp32 from coordinate differences; the smallest d2 wins, the lowest reference index among equal
+ *   d2; a query for which no reference compares below +inf (non-finite coordinates) gets dist +inf and index -1.
+ *   ref_slices: 0 = the library cuts the reference set into slices when batch x query tiles would leave CUs idle, > 0 = forced
+ *   (capped at 64 and at n_ref).  More than one slice needs `scratch` (device memory, m324_nn_plan says how much): each slice
+ *   writes a partial (d2, index) and a second kernel takes the lexicographic minimum -- bit-identical for every slice count.
+ * m324_nn_plan: host-only; returns the slice count m324_nn_search will use for these sizes (or a negative status) and stores the
+ *   scratch size in bytes (slices * batch * n_query * 8) in *scratch_bytes (may be NULL).
+ * ------------------------------------------------------------------------------------------ */
+int m324_nn_plan(int n_query, int n_ref, int batch, int ref_slices, long* scratch_bytes);
+int m324_nn_search(const float* query, long stride_q, int n_query, const float* ref, long stride_r, int n_ref, int batch,
+                   float* dist, int* index, int ref_slices, void* scratch, long scratch_bytes, void* stream);
+/* Per batch item of dist [batch, n] fp32: sum[b] = fp64 sum of the entries, count[b] = number of entries < threshold (compared in
+ * fp64).  +inf / NaN entries propagate into the sum.  partial: device scratch of batch * 64 doubles (32 workgroup partials per
+ * item, added in index order by one thread: deterministic). */
+int m324_dist_stats(const float* dist, int n, int batch, double threshold, double* partial, double* sum, long long* count,
+                    void* stream);
+/* out[i] = s * (R x[i]) + t (= s * (x @ R.T) + t of evaluation_pcd.py:200-202), evaluated in fp64 and rounded once to fp32.
+ * x, out [n, 3] fp32; params = 13 doubles in DEVICE memory: s, R row-major (9), t (3). */
+int m324_transform_points(const float* x, long n, const double* params, float* out, void* stream);
+/* One pass over the source points of an ICP iteration (evaluation_pcd.py:259-270, :361-370, :397-400): st = s * (R src[i]) + t
+ * recomputed in fp64, m = target[index[i]], accumulated in fp64 into record (32 doubles, device):
+ *   [0] n, [1] sum |st - m|, [2..4] sum st, [5..7] sum m, [8..16] sum st (x) m (row = component of st),
+ *   [17..19] sum src, [20..28] sum src (x) m, [29] sum |src|^2, [30..31] zero.
+ * An index outside [0, n_target) makes the sums NaN (nothing is read out of bounds).  partial: device scratch of 64 * 32 doubles
+ * (workgroup partials, added in index order). */
+int m324_icp_moments(const float* src, int n, const double* params, const float* target, int n_target, const int* index,
+                     double* partial, double* record, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

@@ -763,6 +763,108 @@ def nearest_point(query: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
     return idx.long()
 
 
+# ------------------------------------------------------------------------------------------------ geometry evaluation
+def _points(t: torch.Tensor, name: str) -> torch.Tensor:
+    """[n,3] or [B,n,3] point set -> contiguous fp32 device tensor (CPU tensors are refused: there is no host path here)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if t.dim() not in (2, 3) or t.shape[-1] != 3 or t.shape[-2] == 0 or t.shape[0] == 0:
+        raise L.M324Error(f"{name}: expected a non-empty [n,3] or [B,n,3] point set, got {tuple(t.shape)}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def nn_plan(n_query: int, n_ref: int, batch: int = 1, ref_slices: int = 0):
+    """(reference slices, scratch bytes) of the launch m324_nn_search makes for these sizes: m324_nn_plan, host-only"""
+    need = C.c_long(0)
+    slices = int(L.load().m324_nn_plan(n_query, n_ref, batch, ref_slices, C.addressof(need)))
+    L.check(0 if slices > 0 else slices, "m324_nn_plan")
+    return slices, int(need.value)
+
+
+def nn_search(query: torch.Tensor, ref: torch.Tensor, want_dist: bool = True, want_index: bool = False, ref_slices: int = 0):
+    """Nearest reference point of every query point, brute force in fp32 (m324_nn_search).  query / ref: [n,3] or [B,n,3];
+    a 2-D operand beside a 3-D one is shared by every batch item.  Returns the Euclidean distance (fp32), the index (int32,
+    -1 where nothing compares below +inf), or the pair (dist, index) -- shaped [n_query] or [B, n_query]."""
+    q, r = _points(query, "nn_search: query"), _points(ref, "nn_search: ref")
+    if not (want_dist or want_index):
+        raise L.M324Error("nn_search: neither distances nor indices requested")
+    batched = q.dim() == 3 or r.dim() == 3
+    B = q.shape[0] if q.dim() == 3 else (r.shape[0] if r.dim() == 3 else 1)
+    if q.dim() == 3 and r.dim() == 3 and q.shape[0] != r.shape[0]:
+        raise L.M324Error(f"nn_search: batch sizes differ, {tuple(q.shape)} / {tuple(r.shape)}")
+    if q.device != r.device:
+        raise L.M324Error("nn_search: query and ref live on different devices")
+    nq, nr = q.shape[-2], r.shape[-2]
+    stride_q = nq * 3 if q.dim() == 3 else 0
+    stride_r = nr * 3 if r.dim() == 3 else 0
+    slices, need = nn_plan(nq, nr, B, ref_slices)
+    scratch = torch.empty((need,), dtype=torch.uint8, device=q.device) if slices > 1 else None
+    shape = (B, nq) if batched else (nq,)
+    dist = torch.empty(shape, dtype=torch.float32, device=q.device) if want_dist else None
+    index = torch.empty(shape, dtype=torch.int32, device=q.device) if want_index else None
+    L.check(L.load().m324_nn_search(_p(q), stride_q, nq, _p(r), stride_r, nr, B, _p(dist), _p(index), ref_slices, _p(scratch),
+                                    need if slices > 1 else 0, _stream()), "m324_nn_search")
+    _wrote(dist, index)
+    if want_dist and want_index:
+        return dist, index
+    return dist if want_dist else index
+
+
+def dist_stats(dist: torch.Tensor, threshold: float):
+    """dist [n] or [B,n] fp32 -> (fp64 sum, int64 count of entries < threshold) per row, deterministic (m324_dist_stats)."""
+    if not isinstance(dist, torch.Tensor) or not dist.is_cuda:
+        raise L.M324Error("dist_stats: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if dist.dim() not in (1, 2) or dist.numel() == 0 or dist.dtype != torch.float32:
+        raise L.M324Error(f"dist_stats: expected a non-empty fp32 [n] or [B,n] tensor, got {dist.dtype}{tuple(dist.shape)}")
+    d = dist.detach().contiguous()
+    B, n = (d.shape[0], d.shape[1]) if d.dim() == 2 else (1, d.shape[0])
+    partial = torch.empty((B * 64,), dtype=torch.float64, device=d.device)
+    total = torch.empty((B,), dtype=torch.float64, device=d.device)
+    count = torch.empty((B,), dtype=torch.int64, device=d.device)
+    L.check(L.load().m324_dist_stats(_p(d), n, B, float(threshold), _p(partial), _p(total), _p(count), _stream()), "m324_dist_stats")
+    _wrote(partial, total, count)
+    return (total, count) if dist.dim() == 2 else (total[0], count[0])
+
+
+def _transform_params(params: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.float64 or params.numel() != 13 \
+            or not params.is_contiguous():
+        raise L.M324Error(f"{name}: params must be a contiguous fp64 HIP tensor of 13 values (s, R row-major, t)")
+    return params
+
+
+def transform_points(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """s * (x @ R.T) + t for fp32 points [..., 3], evaluated in fp64 and rounded once (m324_transform_points); params =
+    fp64 device tensor (s, R row-major, t)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.M324Error("transform_points: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if x.dim() < 2 or x.shape[-1] != 3 or x.numel() == 0:
+        raise L.M324Error(f"transform_points: expected non-empty [..., 3] points, got {tuple(x.shape)}")
+    xs = x.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(xs)
+    L.check(L.load().m324_transform_points(_p(xs), xs.numel() // 3, _p(_transform_params(params, "transform_points")), _p(out), _stream()),
+            "m324_transform_points")
+    _wrote(out)
+    return out
+
+
+def icp_moments(source: torch.Tensor, params: torch.Tensor, target: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """The fp64 moment record (32 doubles, layout in include/m324.h) of one ICP iteration: source [n,3] fp32 transformed by
+    params, matched to target[index] (m324_icp_moments)."""
+    s, t = _points(source, "icp_moments: source"), _points(target, "icp_moments: target")
+    if s.dim() != 2 or t.dim() != 2:
+        raise L.M324Error(f"icp_moments: expected [n,3] point sets, got {tuple(s.shape)} / {tuple(t.shape)}")
+    if not isinstance(index, torch.Tensor) or not index.is_cuda or index.dtype != torch.int32 or not index.is_contiguous() \
+            or index.numel() != s.shape[0]:
+        raise L.M324Error(f"icp_moments: index must be a contiguous int32 HIP tensor of {s.shape[0]} entries")
+    partial = torch.empty((64 * 32,), dtype=torch.float64, device=s.device)
+    record = torch.empty((32,), dtype=torch.float64, device=s.device)
+    L.check(L.load().m324_icp_moments(_p(s), s.shape[0], _p(_transform_params(params, "icp_moments")), _p(t), t.shape[0], _p(index),
+                                      _p(partial), _p(record), _stream()), "m324_icp_moments")
+    _wrote(partial, record)
+    return record
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
