@@ -394,6 +394,46 @@ int m324_transform_points(const float* x, long n, const double* params, float* o
 int m324_icp_moments(const float* src, int n, const double* params, const float* target, int n_target, const int* index,
                      double* partial, double* record, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Surface sampling (csrc/surface.hip; added at ABI 23 without a bump): area-weighted, seeded samples of a batch of meshes that
+ * share one face list.  replaces: mesh.sample + sample_pointcloud_with_albedo (utils/mesh_processing.py:130-191; the texture
+ * lookup is a Python loop per sample there) and the numpy sampler motion324_amd/preprocess.py sample_surface, whose samples these
+ * entry points reproduce: same (mesh, num, seed), same faces, same points.  All fp64 arithmetic is evaluated without contraction
+ * in the order numpy uses.  Per batch item b the vertices are [n_vertices, 3] fp64 at vertices + b * stride_v (ELEMENTS; 0 = one
+ * mesh for every item); faces [n_faces, 3] int32 are shared.  Vertex indices are NOT checked on the device: the caller
+ * guarantees 0 <= faces < n_vertices (motion324_amd checks before any launch).
+ *
+ * m324_surface_cdf: cdf[b, f] = running sum of the face areas, area = 0.5 * sqrt((cx*cx + cy*cy) + cz*cz) of c = e1 x e2,
+ *   e1 = v1 - v0, e2 = v2 - v0.  The additions run in a fixed nested order that depends on n_faces alone: p = sequential
+ *   inclusive prefix inside each chunk of M324_SURFACE_CHUNK faces; W = sequential exclusive prefix of the chunk totals inside
+ *   each block of M324_SURFACE_BLOCK faces; B = sequential exclusive prefix of the block totals; cdf = fl(B + fl(W + p)).  The
+ *   table is non-decreasing and a face without area repeats its predecessor exactly.  Equal to np.cumsum wherever the partial
+ *   sums are exact.
+ * m324_surface_plan: host-only; returns the number of blocks (or a negative status) and stores the scratch m324_surface_cdf
+ *   needs (device memory, batch * blocks * 8 bytes; 0 for a single block) in *scratch_bytes (may be NULL).
+ * m324_surface_sample: `num` samples per item.  seeds [batch, 2] uint64 (device): the stream seeds of the face draw and of the
+ *   barycentric draw (motion324_amd.synth._stream_seed(seed, "surface.face" / "surface.bary")).  Stream element j of seed s:
+ *   bits = splitmix64(j * 0xD1342543DE82EF95 + s), u = (double)(float)((bits >> 11) * 2^-53) (u = 1 is possible).  Sample i:
+ *   face f = first index with cdf[f] > u_face[i] * cdf[n_faces - 1], at most n_faces - 1 (a bounded binary search; f is in range
+ *   for any table, non-finite entries included); (r0, r1) = elements 2i, 2i + 1 of the barycentric stream, both replaced by
+ *   1 - r when r0 + r1 > 1; point = (v0 + r0 * e1) + r1 * e2.
+ *   points [batch, num, 3] fp32 is required; the rest is skipped when NULL: points64 (the same points before rounding),
+ *   face_index [batch, num] int32, normals [batch, num, 3] fp32 (c / |c| in fp64, zero where |c| = 0), colors [batch, num, 3] fp32.
+ *   Colour source, first match: vertex_colors (uint8 [n_vertices, color_channels], 3 or 4 channels):
+ *   ((c0/255 + c1/255) + c2/255) / 3 in fp64; else uv (fp64 [n_vertices, 2]) with texels (uint8 [tex_h, tex_w, 3]): weights
+ *   (1 - r0 - r1, r0, r1), 1/3 each on a face with |c| = 0, uv = sum w_k * (uv_k mod 1), column (int)clip(uv.x * tex_w, 0,
+ *   tex_w - 1), row (int)clip((1 - uv.y) * tex_h, 0, tex_h - 1), value (float)byte / 255.0f; else 0.5.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_SURFACE_CHUNK 16
+#define M324_SURFACE_BLOCK 1024
+int m324_surface_plan(int n_faces, int batch, long* scratch_bytes);
+int m324_surface_cdf(const double* vertices, long stride_v, int n_vertices, const int* faces, int n_faces, int batch, double* cdf,
+                     void* scratch, long scratch_bytes, void* stream);
+int m324_surface_sample(const double* vertices, long stride_v, int n_vertices, const int* faces, int n_faces, const double* cdf,
+                        const unsigned long long* seeds, int num, int batch, float* points, double* points64, int* face_index,
+                        float* normals, float* colors, const unsigned char* vertex_colors, int color_channels, const double* uv,
+                        const unsigned char* texels, int tex_h, int tex_w, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

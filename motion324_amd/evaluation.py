@@ -5,10 +5,10 @@ Everything expensive in the reference is a cKDTree nearest-neighbour query on th
 iterations), two per frame for the metrics.  Here every query is m324_nn_search (brute force in fp32, csrc/geometry.hip), the
 reductions behind it are m324_dist_stats / m324_icp_moments (fp64, deterministic), and all frames of a sequence go through
 batched launches.  Same function names, argument defaults and return conventions as the reference; arrays or tensors where
-the reference takes trimesh objects.  What stays on the host: the 3x3 SVDs of ICP (numpy), surface sampling
-(preprocess.sample_surface) and file I/O.
+the reference takes trimesh objects.  What stays on the host: the 3x3 SVDs of ICP (numpy), file I/O and, by default, surface
+sampling (preprocess.sample_surface; sampler="device" / --sampler device draws the same samples with m324_surface_sample).
 
-    python -m motion324_amd.evaluation --gt_path GT_DIR --pred_path PRED_DIR [--num_samples 50000] [--seed 0]
+    python -m motion324_amd.evaluation --gt_path GT_DIR --pred_path PRED_DIR [--num_samples 50000] [--seed 0] [--sampler device]
 
 reads two directories in the reference's layout (faces.npy, frame_0000.npy, frame_0001.npy, ...).
 """
@@ -197,13 +197,19 @@ def sample_seed(seed: int, side: int, frame: int) -> int:
     return (int(seed) * 2 + int(side)) * 65536 + int(frame) + 1
 
 
-def evaluate_sequence(gt_vertices, gt_faces, pred_vertices, pred_faces, num_samples=2048, seed=0, threshold=0.02, alignment=None):
+def evaluate_sequence(gt_vertices, gt_faces, pred_vertices, pred_faces, num_samples=2048, seed=0, threshold=0.02, alignment=None,
+                      sampler="host"):
     """Per-frame Chamfer distance and F-score of a predicted mesh sequence against ground truth (evaluation_pcd.py:746-916):
     normalisation parameters from frame 0 of each side; ICP of the normalised predicted frame-0 vertices onto 10 000 surface
     samples of the normalised ground-truth frame 0 (skipped when alignment=(R, t, s) is given); per frame the ground truth is
     normalised and aligned, the prediction normalised, `num_samples` surface points drawn from each, and both metrics computed
     -- all frames in batched launches.  A shorter ground-truth sequence repeats its last frame.
+    sampler="device" draws the per-frame samples on the GPU (preprocess.sample_surface_device: the same samples; one CDF and one
+    sample launch per side for all frames) and hands them to the metrics without a round trip through the host; the per-frame
+    transforms stay the fp64 host arithmetic, and the ICP target samples stay on the host sampler.
     Returns {'chamfer_distances': [...], 'fscores': [...], 'R', 't', 's'}."""
+    if sampler not in ("host", "device"):
+        raise M324Error(f"evaluate_sequence: sampler must be 'host' or 'device', got {sampler!r}")
     gt, pred = _host64(gt_vertices), _host64(pred_vertices)
     gt_faces, pred_faces = np.asarray(gt_faces), np.asarray(pred_faces)
     if gt.ndim != 3 or pred.ndim != 3 or gt.shape[2] != 3 or pred.shape[2] != 3 or len(gt) == 0 or len(pred) == 0:
@@ -221,13 +227,20 @@ def evaluate_sequence(gt_vertices, gt_faces, pred_vertices, pred_faces, num_samp
         R, t, s = alignment
         R, t, s = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64), float(s)
 
-    gt_points = np.empty((num_frames, num_samples, 3), dtype=np.float32)
-    pred_points = np.empty((num_frames, num_samples, 3), dtype=np.float32)
-    for f in range(num_frames):
-        gt_aligned = apply_icp_alignment(apply_normalization(gt[f], gt_center, gt_scale), R, t, s)
-        gt_points[f] = preprocess.sample_surface(gt_aligned, gt_faces, num_samples, sample_seed(seed, 0, f))[0]
-        pred_norm = apply_normalization(pred[f], pred_center, pred_scale)
-        pred_points[f] = preprocess.sample_surface(pred_norm, pred_faces, num_samples, sample_seed(seed, 1, f))[0]
+    if sampler == "device":
+        gt_aligned = np.stack([apply_icp_alignment(apply_normalization(gt[f], gt_center, gt_scale), R, t, s) for f in range(num_frames)])
+        pred_norm = np.stack([apply_normalization(pred[f], pred_center, pred_scale) for f in range(num_frames)])
+        gt_points, _ = preprocess.sample_surface_device(gt_aligned, gt_faces, num_samples, [sample_seed(seed, 0, f) for f in range(num_frames)])
+        pred_points, _ = preprocess.sample_surface_device(pred_norm, pred_faces, num_samples, [sample_seed(seed, 1, f) for f in range(num_frames)],
+                                                          gt_points.device)
+    else:
+        gt_points = np.empty((num_frames, num_samples, 3), dtype=np.float32)
+        pred_points = np.empty((num_frames, num_samples, 3), dtype=np.float32)
+        for f in range(num_frames):
+            gt_aligned = apply_icp_alignment(apply_normalization(gt[f], gt_center, gt_scale), R, t, s)
+            gt_points[f] = preprocess.sample_surface(gt_aligned, gt_faces, num_samples, sample_seed(seed, 0, f))[0]
+            pred_norm = apply_normalization(pred[f], pred_center, pred_scale)
+            pred_points[f] = preprocess.sample_surface(pred_norm, pred_faces, num_samples, sample_seed(seed, 1, f))[0]
     chamfer, fscore = chamfer_and_fscore(gt_points, pred_points, threshold)
     return {"chamfer_distances": [float(c) for c in chamfer.cpu()], "fscores": [float(v) for v in fscore.cpu()], "R": R, "t": t, "s": s}
 
@@ -267,10 +280,12 @@ def main(argv=None) -> dict:
     parser.add_argument("--pred_path", type=str, required=True, help="predicted directory (faces.npy and frame_*.npy)")
     parser.add_argument("--num_samples", type=int, default=50000, help="points sampled from each mesh")
     parser.add_argument("--seed", type=int, default=0, help="seed of the surface samples")
+    parser.add_argument("--sampler", choices=("host", "device"), default="host", help="where the surface samples are drawn (same samples)")
     args = parser.parse_args(argv)
     gt_vertices, gt_faces = load_sequence_dir(args.gt_path)
     pred_vertices, pred_faces = load_sequence_dir(args.pred_path)
-    results = evaluate_sequence(gt_vertices, gt_faces, pred_vertices, pred_faces, num_samples=args.num_samples, seed=args.seed)
+    results = evaluate_sequence(gt_vertices, gt_faces, pred_vertices, pred_faces, num_samples=args.num_samples, seed=args.seed,
+                                sampler=args.sampler)
     for f, (cd, fs) in enumerate(zip(results["chamfer_distances"], results["fscores"])):
         print(f"Frame {f} - Chamfer: {cd:.6f}, F-score: {fs:.4f}")
     print(f"Chamfer Distance - Mean: {np.mean(results['chamfer_distances']):.6f}, Std: {np.std(results['chamfer_distances']):.6f}")

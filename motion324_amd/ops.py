@@ -865,6 +865,112 @@ def icp_moments(source: torch.Tensor, params: torch.Tensor, target: torch.Tensor
     return record
 
 
+# ------------------------------------------------------------------------------------------------ surface sampling
+class SurfaceSamples(NamedTuple):
+    points: torch.Tensor                        # fp32 [num,3] or [B,num,3]
+    points64: Optional[torch.Tensor]            # the same points before rounding
+    face_index: Optional[torch.Tensor]          # int32 [num] or [B,num]
+    normals: Optional[torch.Tensor]             # fp32, like points
+    colors: Optional[torch.Tensor]              # fp32, like points
+
+
+def _device_array(t, dtype: torch.dtype, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if t.dtype != dtype:
+        raise L.M324Error(f"{name}: expected {dtype}, got {t.dtype}")
+    return t.detach().contiguous()
+
+
+def _surface_mesh(vertices, faces, name: str, faces_checked: bool):
+    """(vertices fp64 contiguous, faces int32 contiguous, batch, stride_v in elements, batched); the kernels do not check
+    vertex indices, so the range of `faces` is checked here (one device reduction and a sync) unless the caller did it on the
+    host already."""
+    v = _device_array(vertices, torch.float64, f"{name}: vertices")
+    f = _device_array(faces, torch.int32, f"{name}: faces")
+    if v.dim() not in (2, 3) or v.shape[-1] != 3 or v.shape[-2] == 0 or v.shape[0] == 0:
+        raise L.M324Error(f"{name}: expected non-empty [V,3] or [B,V,3] fp64 vertices, got {tuple(v.shape)}")
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0:
+        raise L.M324Error(f"{name}: expected non-empty [F,3] int32 faces, got {tuple(f.shape)}")
+    if f.device != v.device:
+        raise L.M324Error(f"{name}: vertices and faces live on different devices")
+    if not faces_checked:
+        lo, hi = (int(x) for x in torch.aminmax(f))
+        if lo < 0 or hi >= v.shape[-2]:
+            raise L.M324Error(f"{name}: faces index vertices {lo}..{hi}, the mesh has {v.shape[-2]}")
+    batched = v.dim() == 3
+    return v, f, (v.shape[0] if batched else 1), (v.shape[-2] * 3 if batched else 0), batched
+
+
+def surface_plan(n_faces: int, batch: int = 1):
+    """(face blocks of the scan, scratch bytes) of m324_surface_cdf for these sizes: m324_surface_plan, host-only"""
+    need = C.c_long(0)
+    blocks = int(L.load().m324_surface_plan(n_faces, batch, C.addressof(need)))
+    L.check(0 if blocks > 0 else blocks, "m324_surface_plan")
+    return blocks, int(need.value)
+
+
+def surface_cdf(vertices: torch.Tensor, faces: torch.Tensor, faces_checked: bool = False) -> torch.Tensor:
+    """Area-weighted CDF of the faces (m324_surface_cdf): vertices fp64 [V,3] or [B,V,3], faces int32 [F,3] shared by the batch
+    -> fp64 [F] or [B,F].  The additions run in the fixed nested order of include/m324.h; on a mesh whose partial sums are
+    exact the table equals np.cumsum of the areas."""
+    v, f, B, stride_v, batched = _surface_mesh(vertices, faces, "surface_cdf", faces_checked)
+    nf = f.shape[0]
+    _, need = surface_plan(nf, B)
+    scratch = torch.empty((need,), dtype=torch.uint8, device=v.device) if need else None
+    cdf = torch.empty((B, nf) if batched else (nf,), dtype=torch.float64, device=v.device)
+    L.check(L.load().m324_surface_cdf(_p(v), stride_v, v.shape[-2], _p(f), nf, B, _p(cdf), _p(scratch), need, _stream()), "m324_surface_cdf")
+    _wrote(cdf, scratch)
+    return cdf
+
+
+def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor, seeds: torch.Tensor, num: int, *,
+                   want_points64: bool = False, want_face: bool = True, want_normals: bool = False, want_colors: bool = False,
+                   vertex_colors: Optional[torch.Tensor] = None, uv: Optional[torch.Tensor] = None,
+                   texture: Optional[torch.Tensor] = None, faces_checked: bool = False) -> SurfaceSamples:
+    """`num` surface samples per mesh (m324_surface_sample), the draws of preprocess.sample_surface for the same seeds.
+    vertices / faces / cdf as in surface_cdf; seeds int64 [B,2] (or [2]): the bit patterns of the two uint64 stream seeds.
+    Colours (want_colors) come from vertex_colors (uint8 [V,3|4]) when given, else from uv (fp64 [V,2]) + texture (uint8
+    [H,W,3]), else they are 0.5."""
+    v, f, B, stride_v, batched = _surface_mesh(vertices, faces, "surface_sample", faces_checked)
+    nv, nf, num = v.shape[-2], f.shape[0], int(num)
+    table = _device_array(cdf, torch.float64, "surface_sample: cdf")
+    if tuple(table.shape) != ((B, nf) if batched else (nf,)):
+        raise L.M324Error(f"surface_sample: cdf {tuple(table.shape)} does not match {B} mesh(es) of {nf} faces")
+    sd = _device_array(seeds, torch.int64, "surface_sample: seeds")
+    if sd.numel() != 2 * B or sd.shape[-1] != 2:
+        raise L.M324Error(f"surface_sample: seeds must be int64 [{B},2], got {tuple(sd.shape)}")
+    if num <= 0:
+        raise L.M324Error(f"surface_sample: num must be positive, got {num}")
+    vc = tex = tuv = None
+    channels = tex_h = tex_w = 0
+    if vertex_colors is not None:
+        vc = _device_array(vertex_colors, torch.uint8, "surface_sample: vertex_colors")
+        if vc.dim() != 2 or vc.shape[0] != nv or vc.shape[1] not in (3, 4):
+            raise L.M324Error(f"surface_sample: vertex_colors must be uint8 [{nv},3|4], got {tuple(vc.shape)}")
+        channels = vc.shape[1]
+    elif uv is not None or texture is not None:
+        if uv is None or texture is None:
+            raise L.M324Error("surface_sample: a texture lookup needs both uv and texture")
+        tuv = _device_array(uv, torch.float64, "surface_sample: uv")
+        tex = _device_array(texture, torch.uint8, "surface_sample: texture")
+        if tuple(tuv.shape) != (nv, 2) or tex.dim() != 3 or tex.shape[2] != 3 or tex.shape[0] == 0 or tex.shape[1] == 0:
+            raise L.M324Error(f"surface_sample: expected uv fp64 [{nv},2] and texture uint8 [H,W,3], got {tuple(tuv.shape)} / {tuple(tex.shape)}")
+        tex_h, tex_w = tex.shape[0], tex.shape[1]
+    shape = (B, num) if batched else (num,)
+    dev = v.device
+    points = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+    points64 = torch.empty(shape + (3,), dtype=torch.float64, device=dev) if want_points64 else None
+    face_index = torch.empty(shape, dtype=torch.int32, device=dev) if want_face else None
+    normals = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if want_normals else None
+    colors = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if want_colors else None
+    L.check(L.load().m324_surface_sample(_p(v), stride_v, nv, _p(f), nf, _p(table), _p(sd), num, B, _p(points), _p(points64), _p(face_index),
+                                         _p(normals), _p(colors), _p(vc), channels, _p(tuv), _p(tex), tex_h, tex_w, _stream()),
+            "m324_surface_sample")
+    _wrote(points, points64, face_index, normals, colors)
+    return SurfaceSamples(points, points64, face_index, normals, colors)
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
