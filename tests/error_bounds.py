@@ -444,3 +444,113 @@ def point_encode(proj, ref, out_dtype=torch.bfloat16):
     n = proj.shape[1]
     e[:, :n] = e[:, n:2 * n] = 4 * U32 + 2 * U32 * proj.abs()
     return _round_out(ref, e, out_dtype)
+
+
+# ------------------------------------------------------------------------------------------- optimizer step (fp32 throughout)
+TINY32 = 2.0 ** -126       # smallest normal fp32: what one operation loses at most when its result (or an operand) is flushed to zero
+
+
+def _gamma(k):
+    """k roundings in a row, (1 + U32)^k - 1 <= k U32 / (1 - k U32)"""
+    return k * U32 / (1 - k * U32)
+
+
+def f32(x):
+    """the fp32 value a kernel receives for the Python scalar x (ctypes c_float rounds to nearest), as a Python float"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale):
+    gs = 1.0 if grad_scale is None else float(grad_scale)
+    wd = _f64(weight_decay) if torch.is_tensor(weight_decay) else f32(weight_decay)
+    return f32(lr), f32(beta1), f32(beta2), f32(eps), wd, float(int(step)), gs
+
+
+def adamw_reference(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=None):
+    """One AdamW update in fp64 from the operands the kernels read: fp32 tensors, the fp32 values of the scalars, grad_scale the
+    fp32 device scalar's value (None: 1).  weight_decay: a scalar, or a tensor with one value per element (m324_adamw_flat:
+    weight_decay in front of n_decay, 0 behind it).  Returns (p', m', v')."""
+    p, g, m, v = (_f64(t) for t in (p, g, m, v))
+    lr, b1, b2, eps, wd, t, gs = _adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale)
+    gc = g * gs
+    m2 = b1 * m + (1 - b1) * gc
+    v2 = b2 * v + (1 - b2) * gc * gc
+    den = v2.sqrt() / math.sqrt(1 - b2 ** t) + eps
+    return p * (1 - lr * wd) - lr / (1 - b1 ** t) * m2 / den, m2, v2
+
+
+def adamw_step(p, g, m, v, *, lr, beta1, beta2, eps, weight_decay, step, grad_scale=None):
+    """m324_adamw and m324_adamw_flat (adamw_kernel, adamw_flat_kernel, motion324_amd/csrc/backward.hip): per-element bounds
+    (bp, bm, bv) of one update against adamw_reference, same arguments.  One bound for both kernels -- the first divides by
+    bc2_sqrt, the second multiplies by its rounded reciprocal -- with or without contraction of a product and a sum into an FMA
+    (that only removes roundings).  Derivation, rounding point by rounding point: tests/ERROR_BOUNDS.md, "The optimizer step"."""
+    p, g, m, v = (_f64(t) for t in (p, g, m, v))
+    lr, b1, b2, eps, wd, t, gs = _adamw_scalars(lr, beta1, beta2, eps, weight_decay, step, grad_scale)
+    u = U32
+    p2, m2, v2 = adamw_reference(p, g, m, v, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=wd, step=step, grad_scale=grad_scale)
+    gc = (g * gs).abs()
+    # m' = b1 m + (1 - b1) gc: the two products may cancel, so the error is absolute.  b1 m: its product, the sum (2).
+    # (1 - b1) gc: g gs, 1 - b1, the product, the sum (4).  Four operations whose result may be flushed.
+    e_m = _gamma(2) * b1 * m.abs() + _gamma(4) * (1 - b1) * gc + 4 * TINY32
+    # v' = b2 v + ((1 - b2) gc) gc: both terms are >= 0.  b2 v: 2 roundings; the other: g gs counted twice, 1 - b2, two products,
+    # the sum (6).
+    e_v = _gamma(6) * v2 + 4 * TINY32
+    # host: bc1 = 1 - powf(b1, t), bc2_sqrt = sqrtf(1 - powf(b2, t)): 4 U32 on the transcendental, one rounding of the
+    # difference, the square root halves what is under it and rounds once
+    r_bc1 = 4 * u * b1 ** t / (1 - b1 ** t) + u
+    r_bc2s = 0.5 * (4 * u * b2 ** t / (1 - b2 ** t) + u) + u
+    bc1, bc2s = 1 - b1 ** t, math.sqrt(1 - b2 ** t)
+    # sqrtf(v'): |sqrt a - sqrt b| <= min(|a - b| / sqrt b, sqrt |a - b|); 2 U32 for the device's sqrtf (1 ulp)
+    root = v2.sqrt()
+    e_root = torch.minimum(e_v / root.clamp_min(1e-300), e_v.sqrt()) + 2 * u * root
+    # D = sqrt(v') / bc2_sqrt + eps: the quotient (1 ulp: 2 U32), or the reciprocal (2 U32) and a product (U32) -> 3 U32; the sum
+    e_den = (e_root + (r_bc2s + 3 * u) * root) / bc2s
+    den = root / bc2s + eps
+    e_den = e_den + u * (den + e_den) + TINY32
+    # delta = ((lr / bc1) m') / D: lr / bc1 (2 U32 + r_bc1), the product (U32), the quotient (2 U32)
+    theta = (1 + r_bc1 + 2 * u) * (1 + u) * (1 + 2 * u) / (1 - e_den / den) - 1
+    delta = lr / bc1 * m2 / den
+    e_delta = delta.abs() * theta + (lr / bc1) * e_m / den * (1 + theta) + 2 * TINY32
+    # p (1 - lr wd): lr wd, the difference, the product; then the final difference rounds the value it computed
+    keep = abs(1 - lr * wd)
+    e_keep = u * lr * wd + u * keep * (1 + u)
+    e_pk = p.abs() * (e_keep + u * (keep + e_keep)) + TINY32
+    e_p = e_pk + e_delta
+    e_p = e_p + u * (p2.abs() + e_p) + TINY32
+    return e_p, e_m, e_v
+
+
+def sum_depth(n_per_lane, grid):
+    """longest chain of fp32 additions of the two-kernel sums (grad_sanitize_sumsq_kernel + sum_partial_kernel,
+    motion324_amd/csrc/backward.hip; mse_partial_kernel + mse_final_kernel, motion324_amd/csrc/elementwise.hip): the lane's own
+    running sum, wave_sum's six butterfly steps (motion324_amd/csrc/common.h), red[0] + red[1] + red[2] + red[3], then the final
+    kernel's lane sum over ceil(grid / 64) partials and its wave_sum"""
+    return n_per_lane + 6 + 3 + -(-grid // 64) + 6
+
+
+def grad_sumsq_plan(n, aligned16):
+    """(vec, grid, depth) of m324_grad_sumsq(n) -- the host arithmetic of motion324_amd/csrc/backward.hip, m324_grad_sumsq:
+    `vec = g % 16 == 0 && n >= 4096`, `nb = min(grid_for(vec ? n / 16 : n), 1024)`, grid_for(k) = min(ceil(k / 256), 4096).
+    The 16-byte form adds four squares per unit and lane, and lane k < n % 4 of workgroup 0 one more (the tail)."""
+    vec = bool(aligned16) and n >= 4096
+    k = n // 16 if vec else n
+    grid = min(-(-k // 256), 1024)
+    if vec:
+        per_lane = 4 * -(-(n // 4) // (grid * 256)) + (1 if n % 4 else 0)
+    else:
+        per_lane = -(-n // (grid * 256))
+    return vec, grid, sum_depth(per_lane, grid)
+
+
+def mse_plan(n):
+    """(grid, depth) of m324_mse(n): `nb = min(ceil(n / 256), 1024)` (motion324_amd/csrc/elementwise.hip, m324_mse)"""
+    grid = min(-(-n // 256), 1024)
+    return grid, sum_depth(-(-n // (grid * 256)), grid)
+
+
+def sum_of_squares(total, n, depth, *, term_roundings=1, post_roundings=0):
+    """|fp32 sum - fp64 sum| for a sum of n non-negative terms whose exact total is `total`: every term carries term_roundings
+    roundings of its own (x x: 1; (a - b)^2: 2 for the difference squared, 1 for the product), passes through at most `depth`
+    additions (sum_depth), and post_roundings further operations scale the result.  Non-negative terms: the relative errors add,
+    gamma_k total; n TINY32 for squares that underflow."""
+    return _gamma(depth + term_roundings + post_roundings) * float(total) + n * TINY32

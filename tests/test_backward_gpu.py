@@ -367,6 +367,8 @@ def test_mse_backward_and_cast():
 
 
 def test_adamw_matches_torch_and_grad_norm():
+    """against torch.optim.AdamW over three steps; p', m' and v' element by element against fp64, the flat kernel, the grid-stride
+    loops and the sums at their edges: tests/test_optimizer_gpu.py"""
     from motion324_amd import ops
     torch.manual_seed(0)
     p0, g = _rand((1000,), 27), _rand((1000,), 28)

@@ -10,10 +10,12 @@ arithmetic, bf16 rounding of P / dS / of the output) on the shapes the GPU tests
                (6e-3 / 8e-3 / 2e-2): why a norm gate alone was not enough."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
 import error_bounds as eb
+import optimizer_cases as oc
 from conftest import rel_err
 
 BF = torch.bfloat16
@@ -588,3 +590,118 @@ def test_point_encode_bound():
     bad = out.clone()
     bad[P - 1] = out[P - 2]
     assert int(eb.violations(bad, ref, bound).sum()) >= 40
+
+
+# ------------------------------------------------------------------------------------------- the optimizer step
+def _adamw_check(n, step, gs, form, fma, seed, wd=oc.HYPER["weight_decay"], emu_wd=None, fault=None):
+    """The emulation (decay `emu_wd`, default `wd`; with `fault`, if any) next to the reference and the bound of the CORRECT update
+    with decay `wd` (a scalar or one value per element).  Returns (outs, refs, bounds), each (p', m', v')."""
+    p, g, m, v = oc.adamw_inputs(n, step, seed)
+    hp = dict(oc.HYPER, step=step, weight_decay=wd, grad_scale=None if gs is None else eb.f32(gs))
+    refs, bounds = eb.adamw_reference(p, g, m, v, **hp), eb.adamw_step(p, g, m, v, **hp)
+    emu_wd = wd if emu_wd is None else emu_wd
+    outs = oc.emulate(p.numpy(), g.numpy(), m.numpy(), v.numpy(), form=form, fma=fma, fault=fault,
+                      **dict(hp, grad_scale=gs, weight_decay=emu_wd.numpy() if torch.is_tensor(emu_wd) else emu_wd))
+    return outs, refs, bounds
+
+
+@pytest.mark.parametrize("fma", [False, True])
+@pytest.mark.parametrize("form", ["divide", "reciprocal"])
+def test_adamw_bound_holds_for_both_kernel_forms(form, fma):
+    """soundness: the fp32 emulation of adamw_kernel (divide) and adamw_flat_kernel (reciprocal), contracted or not, inside the
+    bound for p', m' and v' at every step count and gradient scale the GPU tests use"""
+    worst = [0.0, 0.0, 0.0]
+    for step in oc.STEPS:
+        for gs in oc.GRAD_SCALES:
+            outs, refs, bounds = _adamw_check(20000, step, gs, form, fma, seed=100 + step)
+            for i, what in enumerate(("p'", "m'", "v'")):
+                worst[i] = max(worst[i], eb.assert_within(outs[i], refs[i], bounds[i], f"{what} step {step} gs {gs} {form} fma={fma}"))
+    print('worst err / bound (p, m, v):', worst)
+    assert all(0.2 < w <= 1.0 for w in worst), worst            # sound, and not so loose that it could hide a lost rounding
+
+
+def test_adamw_bound_does_not_depend_on_subnormal_flushing():
+    """gradients so small that (1 - b2) g^2 is subnormal or zero: the emulation with gradual underflow and the same results with
+    every subnormal flushed to zero are both inside the bound (its floor of a few smallest normals)"""
+    n = 4096
+    p, _, m, v = oc.adamw_inputs(n, 2, 7)
+    g = (10.0 ** (-22 + 4 * torch.rand(n, generator=torch.Generator().manual_seed(8), dtype=torch.float64))).to(torch.float32)
+    m, v = torch.zeros(n), torch.zeros(n)
+    hp = dict(oc.HYPER, step=1)
+    refs, bounds = eb.adamw_reference(p, g, m, v, **hp), eb.adamw_step(p, g, m, v, **hp)
+    outs = oc.emulate(p.numpy(), g.numpy(), m.numpy(), v.numpy(), **hp)
+    tiny = float(np.finfo(np.float32).tiny)
+    assert int((outs[2] < tiny).sum()) > n // 4                  # the case is there
+    for i, what in enumerate(("p'", "m'", "v'")):
+        eb.assert_within(outs[i], refs[i], bounds[i], what)
+        flushed = torch.where(outs[i].abs() < tiny, torch.zeros_like(outs[i]), outs[i])
+        eb.assert_within(flushed, refs[i], bounds[i], what + " flushed")
+
+
+def test_adamw_decay_boundary_fault_hits_four_elements_and_passes_the_norm_gate():
+    """the hole this bound closes: weight decay applied to the four elements BEHIND n_decay (a 16-byte unit too many) moves four
+    parameters by lr wd = 2e-5 of their value -- exactly those four leave the bound, and `rel_err` over the tensor stays far
+    below the 1e-4 the model-level tests ask of a step"""
+    n, n_decay = 4096 + 4, 2048
+    good_wd, bad_wd = oc.decay_vector(n, n_decay, oc.HYPER["weight_decay"]), oc.decay_vector(n, n_decay + 4, oc.HYPER["weight_decay"])
+    for step in (1, 3):
+        outs, refs, bounds = _adamw_check(n, step, 0.37, "reciprocal", True, seed=5, wd=good_wd, emu_wd=bad_wd)
+        bad = eb.violations(outs[0], refs[0], bounds[0])
+        assert bad.nonzero().flatten().tolist() == [n_decay, n_decay + 1, n_decay + 2, n_decay + 3]
+        assert rel_err(outs[0], refs[0]) < 1e-4
+        assert not eb.violations(outs[1], refs[1], bounds[1]).any() and not eb.violations(outs[2], refs[2], bounds[2]).any()
+        # and the other way round: decay missing on the last four of the decay group
+        outs, refs, bounds = _adamw_check(n, step, 0.37, "reciprocal", True, seed=5, wd=good_wd,
+                                          emu_wd=oc.decay_vector(n, n_decay - 4, oc.HYPER["weight_decay"]))
+        assert eb.violations(outs[0], refs[0], bounds[0]).nonzero().flatten().tolist() == list(range(n_decay - 4, n_decay))
+        assert rel_err(outs[0], refs[0]) < 1e-4
+
+
+@pytest.mark.parametrize("fault,steps,gs,which", [("step", (1, 2, 3), 1.0, 0), ("eps_inside", (1, 3, 100), None, 0),
+                                                  ("m_factor", (1, 3, 20000), 0.37, 1), ("no_scale", (1, 3, 20000), 0.37, 2)])
+def test_adamw_planted_faults_leave_the_bound(fault, steps, gs, which):
+    """power: a step count off by one (bias corrections of the next step), eps added under the bias-corrected square root, m'
+    without its (1 - b1) factor, grad_scale ignored -- each puts elements of p' (and of the moment it touches) outside"""
+    for step in steps:
+        for form in ("divide", "reciprocal"):
+            outs, refs, bounds = _adamw_check(20000, step, gs, form, False, seed=200 + step, fault=fault)
+            n_p = int(eb.violations(outs[0], refs[0], bounds[0]).sum())
+            n_w = int(eb.violations(outs[which], refs[which], bounds[which]).sum())
+            assert n_p > 200 and n_w > 200, (fault, step, form, n_p, n_w)
+
+
+def test_sum_of_squares_bound_and_plans():
+    """the launch arithmetic of m324_grad_sumsq / m324_mse as the builders reproduce it, and an fp32 emulation of the documented
+    summation order (lane sums, butterfly, four waves, final kernel) inside the bound -- a plain 1e-5 * sum is more than four times looser"""
+    assert eb.grad_sumsq_plan(1, True) == (False, 1, 1 + 6 + 3 + 1 + 6)
+    assert eb.grad_sumsq_plan(4095, True)[:2] == (False, 16) and eb.grad_sumsq_plan(4096, True)[:2] == (True, 1)
+    assert eb.grad_sumsq_plan(4096, False)[:2] == (False, 16)
+    assert eb.grad_sumsq_plan(4096 + 3, True) == (True, 1, 4 * 4 + 1 + 6 + 3 + 1 + 6)
+    vec, grid, depth = eb.grad_sumsq_plan(16_777_216 + 5, True)
+    assert (vec, grid) == (True, 1024) and depth == 4 * 17 + 1 + 6 + 3 + 16 + 6       # 4 194 305 units over 262 144 lanes: 17 for lane 0
+    assert eb.mse_plan(255) == (1, 1 + 16) and eb.mse_plan(262_144 + 1) == (1024, 2 + 6 + 3 + 16 + 6)
+    n = 1_000_003
+    x = _rand((n,), 77).numpy()
+    _, grid, depth = eb.grad_sumsq_plan(n, False)
+    lanes = grid * 256
+    sq = np.zeros((-(-n // lanes)) * lanes, dtype=np.float32)
+    sq[:n] = x * x
+    lane = np.zeros(lanes, dtype=np.float32)
+    for row in sq.reshape(-1, lanes):
+        lane = lane + row
+    w = lane.reshape(grid * 4, 64)
+    for s in (1, 2, 4, 8, 16, 32):
+        w = w + w[:, np.arange(64) ^ s]
+    red = w[:, 0].reshape(grid, 4)
+    partial = ((red[:, 0] + red[:, 1]) + red[:, 2]) + red[:, 3]
+    fin = np.zeros(64, dtype=np.float32)
+    pp = np.zeros(-(-grid // 64) * 64, dtype=np.float32)
+    pp[:grid] = partial
+    for row in pp.reshape(-1, 64):
+        fin = fin + row
+    for s in (1, 2, 4, 8, 16, 32):
+        fin = fin + fin[np.arange(64) ^ s]
+    want = float((x.astype(np.float64) ** 2).sum())
+    bound = eb.sum_of_squares(want, n, depth)
+    assert abs(float(fin[0]) - want) <= bound < 1e-5 * want / 4
+    assert abs(float(np.float32(want * (1 + 3e-6))) - want) > bound          # a sum that is off by 3e-6 passed the old gate

@@ -1184,6 +1184,7 @@ def test_linear_n3(dtype):
 
 
 def test_mse():
+    """one shape; the sizes past one workgroup and past the grid cap, with a derived bound: tests/test_optimizer_gpu.py"""
     ops = _ops()
     a, b = _rand((2, 3, 1000, 3), 47), _rand((2, 3, 1000, 3), 48)
     out = ops.mse(a.to(DEV), b.to(DEV), 0.5)
