@@ -434,6 +434,43 @@ int m324_surface_sample(const double* vertices, long stride_v, int n_vertices, c
                         float* normals, float* colors, const unsigned char* vertex_colors, int color_channels, const double* uv,
                         const unsigned char* texels, int tex_h, int tex_w, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Tracked surface samples (csrc/surface.hip; added at ABI 23 without a bump): the samples of m324_surface_sample drawn on frame 0
+ * of a deforming mesh and carried through every frame of the clip, with interpolated vertex normals and a colour from per-corner
+ * UVs.  replaces: track_with_normal_rgb (dataset/dataset_utils.py:44-136; trimesh rebuilds the vertex normals with sparse
+ * products once per frame there) and is defined by the numpy path of motion324_amd/dataset.py track_with_normal_rgb.  As above:
+ * fp64, no contraction, the written order; faces [n_faces, 3] int32 are shared by every frame and item and their range is the
+ * caller's to check.  No atomics: every output is a function of the inputs alone.
+ *
+ * Vertex-corner table (built once per topology, on the host by motion324_amd.ops.vertex_corners): corner 3 f + k is vertex
+ * faces[f][k]; corner_list [3 n_faces] int32 holds the corners grouped by vertex, ascending inside a vertex, and
+ * corner_offsets [n_vertices + 1] int32 the start of every vertex's group (CSR).  An entry outside its range is skipped.
+ * m324_vertex_normals: `frames` poses, frame t at vertices + t * stride_t (ELEMENTS) -> out [frames, n_vertices, 3] fp64.
+ *   Per face, c = e1 x e2 and |c| as in m324_surface_cdf; a face with |c| = 0 contributes nothing.  Corner k of face f adds
+ *   w * (c / |c|) (per component) to its vertex; a vertex's corners are added one after the other in the table's order, starting
+ *   from 0.  out = n / |n| with |n| = sqrt((nx*nx + ny*ny) + nz*nz), exactly 0 where |n| = 0 (a vertex without faces included).
+ *   M324_NORMALS_ANGLE (what trimesh's vertex_normals documents): w = the face's angle at the corner.  With u = e1 / |e1|,
+ *   q = e2 / |e2|, p = (v2 - v1) / |v2 - v1| (norms and dot products summed as |c| is): angle0 = acos(clip(u.q, -1, 1)),
+ *   angle1 = acos(clip(-(u.p), -1, 1)), angle2 = (pi - angle0) - angle1.  M324_NORMALS_AREA: w = 0.5 * |c|.
+ * m324_surface_track: cdf [batch, n_faces] is m324_surface_cdf of every item's FRAME 0, seeds as for m324_surface_sample, and
+ *   face f and (r0, r1) of sample i are m324_surface_sample's.  Frame t of item b is at vertices + b * stride_b + t * stride_t
+ *   (ELEMENTS; stride_b = 0: one clip for every item).  points [batch, frames, num, 3] fp32 = (v0 + r0 * e1) + r1 * e2 on frame
+ *   t's vertices (frame 0 repeats m324_surface_sample); skipped when NULL: points64 (before rounding), face_index [batch, num].
+ *   normals [batch, frames, num, 3] fp32 with vertex_normals (fp64 [n_vertices, 3] at + b * normal_stride_b + t * normal_stride_t),
+ *   both or neither: m = (w0 * n0 + r0 * n1) + r1 * n2 per component, w0 = (1 - r0) - r1; the output is m / |m|, and m where
+ *   |m| = 0.  colors [batch, num, 3] fp32 with face_uvs (fp64 [n_faces, 3, 2]) and texels (uint8 [tex_h, tex_w, 3]), all or none:
+ *   (u, v) = (w0 * uv0 + r0 * uv1) + r1 * uv2, column (int)clip(u * (tex_w - 1), 0, tex_w - 1), row (int)clip((1 - v) *
+ *   (tex_h - 1), 0, tex_h - 1), a NaN lands on 0, value (float)((double)byte / 255.0) -- the dataset's rule: no wrap, size - 1.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_NORMALS_ANGLE 0
+#define M324_NORMALS_AREA 1
+int m324_vertex_normals(const double* vertices, long stride_t, int n_vertices, const int* faces, int n_faces, const int* corner_offsets,
+                        const int* corner_list, int frames, int weighting, double* out, void* stream);
+int m324_surface_track(const double* vertices, long stride_b, long stride_t, int n_vertices, const int* faces, int n_faces, const double* cdf,
+                       const unsigned long long* seeds, int num, int batch, int frames, float* points, double* points64, int* face_index,
+                       const double* vertex_normals, long normal_stride_b, long normal_stride_t, float* normals, const double* face_uvs,
+                       const unsigned char* texels, int tex_h, int tex_w, float* colors, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

@@ -214,6 +214,155 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void surface_sample_kernel(
     }
 }
 
+// ------------------------------------------------------------------------------------------------ tracked samples
+// The draw of surface_sample_kernel for sample i of an item, restated for the kernels that follow a sample through a clip: the
+// same hash, the same bounded search of the frame-0 CDF row, the same reflection of the barycentric pair.
+__device__ __forceinline__ int draw_sample(const double* __restrict__ row, int n_faces, unsigned long long seed_face,
+                                           unsigned long long seed_bary, int i, double& r0, double& r1) {
+    const double target = stream_uniform(seed_face, (unsigned long long)i) * row[n_faces - 1];
+    int lo = 0, hi = n_faces;
+    for (int step = 0; step < 32 && lo < hi; ++step) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (row[mid] > target) hi = mid; else lo = mid + 1;
+    }
+    r0 = stream_uniform(seed_bary, 2ULL * (unsigned long long)i);
+    r1 = stream_uniform(seed_bary, 2ULL * (unsigned long long)i + 1ULL);
+    if (r0 + r1 > 1.0) {
+        r0 = 1.0 - r0;
+        r1 = 1.0 - r1;
+    }
+    return min(max(lo, 0), n_faces - 1);
+}
+
+__device__ __forceinline__ double norm3(const double (&a)[3]) { return __dsqrt_rn((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]); }
+__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+// np.clip(x, -1, 1): a NaN stays a NaN
+__device__ __forceinline__ double clip_unit(double x) { return x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x); }
+
+constexpr int NORMAL_THREADS = 256;                      // (frame, vertex) pairs per workgroup of vertex_normals_kernel
+constexpr double PI = 3.141592653589793;                 // np.pi
+
+// One lane = one vertex of one frame: it walks the vertex's corners in ascending order and adds each face's weighted unit normal
+// to a running sum of its own -- a gather, so the order of the additions is the table's and nothing depends on scheduling.  A
+// vertex of valence k recomputes k cross products (each face is visited by its three vertices); no per-face buffer, no
+// per-vertex buffer, any valence.  Entries of the table outside their range are skipped, so a bad table reads nothing out of bounds.
+template <int WEIGHTING>
+__global__ __launch_bounds__(NORMAL_THREADS) void vertex_normals_kernel(const double* __restrict__ vertices, long stride_t, int n_vertices,
+                                                                        const int* __restrict__ faces, int n_faces,
+                                                                        const int* __restrict__ corner_offsets,
+                                                                        const int* __restrict__ corner_list, long total,
+                                                                        double* __restrict__ out) {
+    const long g = (long)blockIdx.x * NORMAL_THREADS + threadIdx.x;
+    if (g >= total) return;
+    const int t = (int)(g / n_vertices);
+    const int vtx = (int)(g % n_vertices);
+    const double* v = vertices + (long)t * stride_t;
+    const long n_corners = 3L * n_faces;
+    const long lo = max(corner_offsets[vtx], 0);
+    const long hi = min((long)corner_offsets[vtx + 1], n_corners);
+    double n[3] = {0.0, 0.0, 0.0};
+    for (long at = lo; at < hi; ++at) {
+        const int corner = corner_list[at];
+        if (corner < 0 || corner >= n_corners) continue;
+        const int f = corner / 3, k = corner - 3 * f;
+        const Tri tri = load_tri(v, faces, f);
+        double c[3];
+        const double ln = cross_norm(tri, c);
+        if (!(ln != 0.0)) continue;                          // a face without area contributes nothing
+        double w;
+        if (WEIGHTING == M324_NORMALS_AREA) {
+            w = 0.5 * ln;
+        } else {
+            const double l1 = norm3(tri.e1), l2 = norm3(tri.e2);
+            double u[3], q[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) u[a] = tri.e1[a] / l1;
+            double a0 = 0.0, a1 = 0.0;
+            if (k != 1) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) q[a] = tri.e2[a] / l2;
+                a0 = acos(clip_unit(dot3(u, q)));
+            }
+            if (k != 0) {
+                const long i1 = faces[(long)f * 3 + 1], i2 = faces[(long)f * 3 + 2];
+                double e3[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) e3[a] = v[i2 * 3 + a] - v[i1 * 3 + a];   // v2 - v1 itself: e2 - e1 rounds differently
+                const double l3 = norm3(e3);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) q[a] = e3[a] / l3;
+                a1 = acos(clip_unit(-dot3(u, q)));
+            }
+            w = k == 0 ? a0 : (k == 1 ? a1 : (PI - a0) - a1);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) n[a] = n[a] + w * (c[a] / ln);
+    }
+    const double len = norm3(n);
+    double* o = out + g * 3;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) o[a] = len != 0.0 ? n[a] / len : 0.0;
+}
+
+// One work item = (batch item, group of `frames_per_group` frames, tile of SAMPLE_THREADS samples) of a flat grid, one sample per
+// lane.  The lane draws its face and weights once (draw_sample), keeps the three vertex indices and walks its frames; every
+// (sample, frame) output is a function of the inputs alone, so the grouping -- chosen on the host to fill the chip -- never
+// shows in the results.  Group 0 writes what has no frame axis (face index, colour).
+__global__ __launch_bounds__(SAMPLE_THREADS) void surface_track_kernel(
+    const double* __restrict__ vertices, long stride_b, long stride_t, const int* __restrict__ faces, int n_faces,
+    const double* __restrict__ cdf, const unsigned long long* __restrict__ seeds, int num, int frames, int frames_per_group, int groups,
+    int tiles, float* __restrict__ points, double* __restrict__ points64, int* __restrict__ face_index,
+    const double* __restrict__ vertex_normals, long normal_stride_b, long normal_stride_t, float* __restrict__ normals,
+    const double* __restrict__ face_uvs, const unsigned char* __restrict__ texels, int tex_h, int tex_w, float* __restrict__ colors) {
+    const int tile = blockIdx.x % tiles;
+    const int group = (blockIdx.x / tiles) % groups;
+    const int b = blockIdx.x / (tiles * groups);
+    const int i = tile * SAMPLE_THREADS + threadIdx.x;
+    if (i >= num) return;
+    double r0, r1;
+    const int f = draw_sample(cdf + (long)b * n_faces, n_faces, seeds[(long)b * 2], seeds[(long)b * 2 + 1], i, r0, r1);
+    const long i0 = faces[(long)f * 3], i1 = faces[(long)f * 3 + 1], i2 = faces[(long)f * 3 + 2];
+    const double w0 = (1.0 - r0) - r1;
+
+    if (group == 0) {
+        if (face_index) face_index[(long)b * num + i] = f;
+        if (colors) {
+            const double* uv = face_uvs + (long)f * 6;
+            const double s = (w0 * uv[0] + r0 * uv[2]) + r1 * uv[4];
+            const double t = (w0 * uv[1] + r0 * uv[3]) + r1 * uv[5];
+            const int col = clip_index(s * (double)(tex_w - 1), tex_w);
+            const int rw = clip_index((1.0 - t) * (double)(tex_h - 1), tex_h);
+            const unsigned char* px = texels + ((long)rw * tex_w + col) * 3;
+            float* o = colors + ((long)b * num + i) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = (float)((double)px[k] / 255.0);
+        }
+    }
+
+    const int t_end = min(frames, (group + 1) * frames_per_group);
+    for (int t = group * frames_per_group; t < t_end; ++t) {
+        const double* v = vertices + (long)b * stride_b + (long)t * stride_t;
+        const long o = (((long)b * frames + t) * num + i) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v0 = v[i0 * 3 + c];
+            const double e1 = v[i1 * 3 + c] - v0, e2 = v[i2 * 3 + c] - v0;
+            const double x = (v0 + r0 * e1) + r1 * e2;
+            points[o + c] = (float)x;
+            if (points64) points64[o + c] = x;
+        }
+        if (normals) {
+            const double* vn = vertex_normals + (long)b * normal_stride_b + (long)t * normal_stride_t;
+            double m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = (w0 * vn[i0 * 3 + c] + r0 * vn[i1 * 3 + c]) + r1 * vn[i2 * 3 + c];
+            const double len = norm3(m);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) normals[o + c] = (float)(len == 0.0 ? m[c] : m[c] / len);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int m324_surface_plan(int n_faces, int batch, long* scratch_bytes) {
@@ -280,5 +429,55 @@ extern "C" int m324_surface_sample(const double* vertices, long stride_v, int n_
     }
 #undef SURFACE_LAUNCH
     M324_CHECK_LAUNCH("m324_surface_sample");
+    return M324_OK;
+}
+
+extern "C" int m324_vertex_normals(const double* vertices, long stride_t, int n_vertices, const int* faces, int n_faces,
+                                   const int* corner_offsets, const int* corner_list, int frames, int weighting, double* out, void* stream) {
+    M324_REQUIRE(vertices && faces && corner_offsets && corner_list && out,
+                 "m324_vertex_normals: null vertices, faces, corner_offsets, corner_list or out");
+    M324_REQUIRE(n_vertices > 0 && n_faces > 0 && frames > 0 && stride_t >= 0 && n_faces <= 2147483647 / 3,
+                 "m324_vertex_normals: sizes must be positive (n_vertices=%d n_faces=%d frames=%d stride_t=%ld)", n_vertices, n_faces, frames, stride_t);
+    M324_REQUIRE(weighting == M324_NORMALS_ANGLE || weighting == M324_NORMALS_AREA, "m324_vertex_normals: weighting must be %d (angle) or %d (area), got %d",
+                 M324_NORMALS_ANGLE, M324_NORMALS_AREA, weighting);
+    const long total = (long)frames * n_vertices;
+    M324_REQUIRE((total + NORMAL_THREADS - 1) / NORMAL_THREADS < 2147483647L, "m324_vertex_normals: frames * n_vertices too large");
+    const dim3 grid(ceil_div(total, NORMAL_THREADS)), block(NORMAL_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (weighting == M324_NORMALS_AREA)
+        hipLaunchKernelGGL(vertex_normals_kernel<M324_NORMALS_AREA>, grid, block, 0, st, vertices, stride_t, n_vertices, faces, n_faces, corner_offsets,
+                           corner_list, total, out);
+    else
+        hipLaunchKernelGGL(vertex_normals_kernel<M324_NORMALS_ANGLE>, grid, block, 0, st, vertices, stride_t, n_vertices, faces, n_faces, corner_offsets,
+                           corner_list, total, out);
+    M324_CHECK_LAUNCH("m324_vertex_normals");
+    return M324_OK;
+}
+
+extern "C" int m324_surface_track(const double* vertices, long stride_b, long stride_t, int n_vertices, const int* faces, int n_faces,
+                                  const double* cdf, const unsigned long long* seeds, int num, int batch, int frames, float* points,
+                                  double* points64, int* face_index, const double* vertex_normals, long normal_stride_b, long normal_stride_t,
+                                  float* normals, const double* face_uvs, const unsigned char* texels, int tex_h, int tex_w, float* colors,
+                                  void* stream) {
+    M324_REQUIRE(vertices && faces && cdf && seeds && points, "m324_surface_track: null vertices, faces, cdf, seeds or points");
+    M324_REQUIRE(n_vertices > 0 && n_faces > 0 && num > 0 && batch > 0 && frames > 0 && stride_b >= 0 && stride_t >= 0,
+                 "m324_surface_track: sizes must be positive (n_vertices=%d n_faces=%d num=%d batch=%d frames=%d stride_b=%ld stride_t=%ld)", n_vertices,
+                 n_faces, num, batch, frames, stride_b, stride_t);
+    M324_REQUIRE(!normals == !vertex_normals && normal_stride_b >= 0 && normal_stride_t >= 0,
+                 "m324_surface_track: normals and vertex_normals go together, with non-negative strides (%ld, %ld)", normal_stride_b, normal_stride_t);
+    M324_REQUIRE(colors ? (face_uvs && texels && tex_h > 0 && tex_w > 0) : (!face_uvs && !texels),
+                 "m324_surface_track: colors, face_uvs and texels of a positive size (%d x %d) go together", tex_h, tex_w);
+    const int tiles = ceil_div(num, SAMPLE_THREADS);
+    // frames per lane: as many as still leave four workgroups per compute unit, so a single long clip spreads over the chip and a
+    // large batch amortises the draw.  The results do not depend on it.
+    const long items = (long)batch * tiles * frames;
+    long per = items / (4L * m324::cu_count());
+    per = per < 1 ? 1 : (per > frames ? frames : per);
+    const int groups = ceil_div(frames, per);
+    M324_REQUIRE((long)batch * tiles * groups < 2147483647L, "m324_surface_track: batch * frame groups * sample tiles too large");
+    hipLaunchKernelGGL(surface_track_kernel, dim3(batch * groups * tiles), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, vertices, stride_b, stride_t,
+                       faces, n_faces, cdf, seeds, num, frames, (int)per, groups, tiles, points, points64, face_index, vertex_normals, normal_stride_b,
+                       normal_stride_t, normals, face_uvs, texels, tex_h, tex_w, colors);
+    M324_CHECK_LAUNCH("m324_surface_track");
     return M324_OK;
 }

@@ -971,6 +971,151 @@ def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tenso
     return SurfaceSamples(points, points64, face_index, normals, colors)
 
 
+# ------------------------------------------------------------------------------------------------ tracked surface samples
+class VertexCorners(NamedTuple):
+    offsets: torch.Tensor                       # int32 [V+1]: start of every vertex's group in `corners`
+    corners: torch.Tensor                       # int32 [3F]: corners 3 f + k grouped by vertex, ascending inside a vertex
+
+
+class TrackedSamples(NamedTuple):
+    points: torch.Tensor                        # fp32 [T,num,3] or [B,T,num,3]
+    normals: Optional[torch.Tensor]             # fp32, like points
+    colors: Optional[torch.Tensor]              # fp32 [num,3] or [B,num,3]: a sample keeps its colour through the clip
+    face_index: Optional[torch.Tensor]          # int32 [num] or [B,num]
+    points64: Optional[torch.Tensor] = None     # the same points before rounding
+
+
+NORMAL_WEIGHTINGS = {"angle": 0, "area": 1}    # M324_NORMALS_ANGLE, M324_NORMALS_AREA
+_CORNER_CACHE = {}                              # id(faces) -> (weakref to faces, its version, n_vertices, VertexCorners)
+
+
+def vertex_corners(faces: torch.Tensor, n_vertices: int) -> VertexCorners:
+    """The vertex-corner table of include/m324.h for faces int32 [F,3] on the device: a stable counting sort of the corners by
+    vertex, done in numpy on the host (one download of the faces; their range is checked on the way) and cached on the identity
+    and version of the faces tensor -- the table depends on the topology alone, so a mesh pays for it once."""
+    import weakref
+    import numpy as np
+    f = _device_array(faces, torch.int32, "vertex_corners: faces")
+    n_vertices = int(n_vertices)
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0 or n_vertices <= 0 or f.shape[0] > (2 ** 31 - 1) // 3:
+        raise L.M324Error(f"vertex_corners: expected non-empty [F,3] int32 faces and a positive vertex count, got {tuple(f.shape)} / {n_vertices}")
+    hit = _CORNER_CACHE.get(id(faces))
+    if hit is not None and hit[0]() is faces and hit[1] == faces._version and hit[2] == n_vertices:
+        return hit[3]
+    flat = f.cpu().numpy().reshape(-1)
+    if flat.min() < 0 or flat.max() >= n_vertices:
+        raise L.M324Error(f"vertex_corners: faces index vertices {flat.min()}..{flat.max()}, the mesh has {n_vertices}")
+    offsets = np.zeros(n_vertices + 1, dtype=np.int64)
+    np.cumsum(np.bincount(flat, minlength=n_vertices), out=offsets[1:])
+    corners = np.argsort(flat, kind="stable")                                   # ascending corner index inside a vertex
+    table = VertexCorners(torch.from_numpy(offsets.astype(np.int32)).to(f.device), torch.from_numpy(corners.astype(np.int32)).to(f.device))
+    key = id(faces)
+    _CORNER_CACHE[key] = (weakref.ref(faces, lambda _, key=key: _CORNER_CACHE.pop(key, None)), faces._version, n_vertices, table)
+    return table
+
+
+def _corner_table(corners, faces: torch.Tensor, f: torch.Tensor, n_vertices: int, name: str) -> VertexCorners:
+    """the caller's table, shape-checked against the mesh, or the cached one of the caller's faces tensor (f: its contiguous form)"""
+    if corners is None:
+        return vertex_corners(faces, n_vertices)
+    if not isinstance(corners, tuple) or len(corners) != 2:
+        raise L.M324Error(f"{name}: corners is what vertex_corners returns: (offsets int32 [V+1], corners int32 [3F])")
+    off = _device_array(corners[0], torch.int32, f"{name}: corner offsets")
+    lst = _device_array(corners[1], torch.int32, f"{name}: corner list")
+    if tuple(off.shape) != (n_vertices + 1,) or tuple(lst.shape) != (3 * f.shape[0],) or off.device != f.device or lst.device != f.device:
+        raise L.M324Error(f"{name}: the corner table {tuple(off.shape)} / {tuple(lst.shape)} does not fit {n_vertices} vertices and "
+                          f"{f.shape[0]} faces")
+    return VertexCorners(off, lst)
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, corners: Optional[VertexCorners] = None, weighting: str = "angle",
+                   faces_checked: bool = False) -> torch.Tensor:
+    """Unit vertex normals of every pose of one topology (m324_vertex_normals): vertices fp64 [V,3] or [..., V, 3] (any leading
+    axes: frames, batch x frames), faces int32 [F,3] -> fp64 like vertices.  weighting "angle" (trimesh's default) or "area";
+    corners: vertex_corners(faces, V), built (and cached) here when omitted.  A vertex without faces, or whose sum is zero, gets 0."""
+    if weighting not in NORMAL_WEIGHTINGS:
+        raise L.M324Error(f"vertex_normals: weighting must be one of {sorted(NORMAL_WEIGHTINGS)}, got {weighting!r}")
+    v = _device_array(vertices, torch.float64, "vertex_normals: vertices")
+    if v.dim() < 2 or v.shape[-1] != 3 or v.numel() == 0:
+        raise L.M324Error(f"vertex_normals: expected non-empty fp64 vertices [..., V, 3], got {tuple(v.shape)}")
+    nv = v.shape[-2]
+    _, f, _, _, _ = _surface_mesh(v.reshape(-1, nv, 3)[0], faces, "vertex_normals", faces_checked)
+    table = _corner_table(corners, faces, f, nv, "vertex_normals")
+    frames = v.numel() // (nv * 3)
+    out = torch.empty_like(v)
+    L.check(L.load().m324_vertex_normals(_p(v), nv * 3, nv, _p(f), f.shape[0], _p(table.offsets), _p(table.corners), frames,
+                                         NORMAL_WEIGHTINGS[weighting], _p(out), _stream()), "m324_vertex_normals")
+    _wrote(out)
+    return out
+
+
+def surface_track(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor, seeds: torch.Tensor, num: int, *,
+                  vertex_normals: Optional[torch.Tensor] = None, face_uvs: Optional[torch.Tensor] = None,
+                  texture: Optional[torch.Tensor] = None, frames: Optional[int] = None, want_points64: bool = False,
+                  want_face: bool = True, faces_checked: bool = False) -> TrackedSamples:
+    """`num` surface samples drawn on frame 0 and carried through every frame (m324_surface_track): frame 0 repeats
+    surface_sample for the same seeds.  vertices fp64 [T,V,3] (one clip) or [B,T,V,3]; faces int32 [F,3]; cdf = surface_cdf of
+    frame 0, [F] or [B,F]; seeds int64 [2] or [B,2].  One clip with B > 1 seeds draws B sample sets on it (batch stride 0).
+    vertex_normals (fp64, shaped like vertices) adds interpolated unit normals; face_uvs (fp64 [F,3,2]) with texture (uint8
+    [H,W,3]) adds one colour per sample.  frames: track only the first `frames` frames of the clip (the outputs have that many);
+    the clip is addressed in place by its strides, so frames=1 draws on frame 0 without a copy of it."""
+    v = _device_array(vertices, torch.float64, "surface_track: vertices")
+    if v.dim() not in (3, 4) or v.shape[-1] != 3 or v.numel() == 0:
+        raise L.M324Error(f"surface_track: expected non-empty fp64 vertices [T,V,3] or [B,T,V,3], got {tuple(v.shape)}")
+    T, nv = v.shape[-3], v.shape[-2]
+    stride_t = nv * 3
+    if frames is not None:
+        if not 1 <= int(frames) <= T:
+            raise L.M324Error(f"surface_track: frames must be in 1..{T} for vertices {tuple(v.shape)}, got {frames}")
+        T = int(frames)
+    _, f, _, _, _ = _surface_mesh(v.reshape(-1, nv, 3)[0], faces, "surface_track", faces_checked)
+    nf, num = f.shape[0], int(num)
+    sd = _device_array(seeds, torch.int64, "surface_track: seeds")
+    if sd.dim() not in (1, 2) or sd.shape[-1] != 2 or sd.numel() == 0:
+        raise L.M324Error(f"surface_track: seeds must be int64 [2] or [B,2], got {tuple(sd.shape)}")
+    batched = v.dim() == 4 or sd.dim() == 2
+    B = sd.numel() // 2
+    if v.dim() == 4 and v.shape[0] != B:
+        raise L.M324Error(f"surface_track: {B} seed pair(s) for vertices {tuple(v.shape)}")
+    stride_b = v.shape[-3] * stride_t if v.dim() == 4 else 0
+    table = _device_array(cdf, torch.float64, "surface_track: cdf")
+    if tuple(table.shape) not in (((B, nf), (nf,)) if stride_b == 0 else ((B, nf),)):
+        raise L.M324Error(f"surface_track: cdf {tuple(table.shape)} does not match {B} item(s) of {nf} faces on vertices {tuple(v.shape)}")
+    if table.dim() == 1 and B > 1:
+        table = table.expand(B, nf).contiguous()
+    if num <= 0:
+        raise L.M324Error(f"surface_track: num must be positive, got {num}")
+    vn = None
+    if vertex_normals is not None:
+        vn = _device_array(vertex_normals, torch.float64, "surface_track: vertex_normals")
+        if vn.shape != v.shape:
+            raise L.M324Error(f"surface_track: vertex_normals {tuple(vn.shape)} must be shaped like vertices {tuple(v.shape)}")
+    tuv = tex = None
+    tex_h = tex_w = 0
+    if face_uvs is not None or texture is not None:
+        if face_uvs is None or texture is None:
+            raise L.M324Error("surface_track: a colour lookup needs both face_uvs and texture")
+        tuv = _device_array(face_uvs, torch.float64, "surface_track: face_uvs")
+        tex = _device_array(texture, torch.uint8, "surface_track: texture")
+        if tuple(tuv.shape) != (nf, 3, 2) or tex.dim() != 3 or tex.shape[2] != 3 or tex.shape[0] == 0 or tex.shape[1] == 0:
+            raise L.M324Error(f"surface_track: expected face_uvs fp64 [{nf},3,2] and texture uint8 [H,W,3], got {tuple(tuv.shape)} / {tuple(tex.shape)}")
+        tex_h, tex_w = tex.shape[0], tex.shape[1]
+    if any(t is not None and t.device != v.device for t in (f, sd, table, vn, tuv, tex)):
+        raise L.M324Error("surface_track: the inputs live on different devices")
+    lead = (B,) if batched else ()
+    dev = v.device
+    points = torch.empty(lead + (T, num, 3), dtype=torch.float32, device=dev)
+    points64 = torch.empty(lead + (T, num, 3), dtype=torch.float64, device=dev) if want_points64 else None
+    face_index = torch.empty(lead + (num,), dtype=torch.int32, device=dev) if want_face else None
+    normals = torch.empty(lead + (T, num, 3), dtype=torch.float32, device=dev) if vn is not None else None
+    colors = torch.empty(lead + (num, 3), dtype=torch.float32, device=dev) if tex is not None else None
+    L.check(L.load().m324_surface_track(_p(v), stride_b, stride_t, nv, _p(f), nf, _p(table), _p(sd), num, B, T, _p(points), _p(points64),
+                                        _p(face_index), _p(vn), stride_b, stride_t, _p(normals), _p(tuv), _p(tex), tex_h, tex_w, _p(colors),
+                                        _stream()), "m324_surface_track")
+    _wrote(points, points64, face_index, normals, colors)
+    return TrackedSamples(points, normals, colors, face_index, points64)
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
