@@ -471,6 +471,58 @@ int m324_surface_track(const double* vertices, long stride_b, long stride_t, int
                        const double* vertex_normals, long normal_stride_b, long normal_stride_t, float* normals, const double* face_uvs,
                        const unsigned char* texels, int tex_h, int tex_w, float* colors, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Video framing (csrc/framing.hip; added at ABI 23 without a bump): a matted video becomes the foreground-centred square clip
+ * the model was trained on.  replaces: compute_mask_bbox / merge_bbox / crop_and_center_to_512 and the masking of
+ * utils/rmbg_for_black_bg.py (a PIL loop per frame) and the soft masking of utils/inference_utils.py:279.  All arithmetic is
+ * integer, so the results are the reference's bit for bit.  Images are uint8; every stride is in BYTES.  Pixel (t, y, x) of the
+ * source is at src + t * src_frame + y * src_pitch + x * src_pixel, its alpha at alpha + t * alpha_frame + y * alpha_pitch +
+ * x * alpha_pixel.
+ *
+ * Masking modes.  M324_FRAME_THRESHOLD: m = alpha > threshold ? 255 : 0, value = m ? value : 0.  M324_FRAME_SOFT: m = alpha,
+ *   value = table[alpha * 256 + value] (table: 65536 bytes in DEVICE memory, built by the caller).  For m324_frame_resample
+ *   only: M324_FRAME_NONE (the source as it is; alpha unused) and M324_FRAME_BINARY (every channel = alpha > threshold ? 255 : 0;
+ *   the source values are not read: the 0 / 255 mask image of the threshold mode, made on the fly from the alpha plane).
+ * m324_frame_mask: `frames` images of height x width pixels, three colour bytes per pixel at a pixel stride of 3 or 4.  alpha
+ *   NULL = RGBA: the fourth byte of every pixel (src_pixel must be 4; the alpha strides are ignored).  Optional outputs (NULL =
+ *   skipped), both dense: masked [frames, height, width, 3], mask [frames, height, width].  Always written: boxes [frames, 4]
+ *   int32 = (min x, min y, max x + 1, max y + 1) over the pixels with m > 0; a frame without one keeps (width, height, 0, 0),
+ *   i.e. left >= right.  The entry point initialises boxes; the kernel reduces per wave, per workgroup, then with integer
+ *   atomic min / max, so the result does not depend on the order.  Groups of 16 pixels move as 16-byte accesses wherever their
+ *   addresses are 16-byte aligned and byte by byte elsewhere: any pitch works.
+ * m324_frame_resample: ONE separable pass of Pillow's 8-bit resampling over the crop [crop_x, crop_x + crop_w) x [crop_y,
+ *   crop_y + crop_h) of `frames` images of src_w x src_h pixels with `channels` (1 or 3) bytes per pixel.  axis =
+ *   M324_FRAME_AXIS_X resamples along x (in_size = crop_w; the result is out_size x crop_h pixels), M324_FRAME_AXIS_Y along y
+ *   (in_size = crop_h; crop_w x out_size).  coef [out_size, ksize] and bounds [out_size, 2] int32 (device): output i reads the
+ *   bounds[i][1] <= ksize source samples from bounds[i][0] on (positions inside the crop; out-of-range entries are clamped, so a
+ *   bad table reads nothing out of bounds):
+ *     acc = 1 << 21; acc += value * coef[i][k] for every tap k; out = clamp(acc >> 22, 0, 255)
+ *   in 32-bit two's complement with an arithmetic shift.  The masking mode is applied to every source value before the taps.
+ *   The result is pasted at (paste_x, paste_y) of the dst_w x dst_h destination.  fill = -1: only the pasted region is
+ *   written; fill = 0..255: the WHOLE destination is written, `fill` outside the region (no separate clear).  Each workgroup
+ *   stages the source span of its outputs in LDS once, masked.  in_size <= M324_FRAME_MAX_SIDE: one source line of three
+ *   channels is 48 KB, which is what a workgroup can stage when its outputs need all of it.
+ * m324_frame_plan: host-only; returns ksize = 2 * ceil(3 * max(in_size / out_size, 1)) + 1 (or a negative status) and stores
+ *   the bytes of the pass's result, frames * lines * out_size * channels, in *scratch_bytes (may be NULL): the intermediate
+ *   between the two passes.  Refuses non-positive sizes, channels other than 1 or 3 and in_size > M324_FRAME_MAX_SIDE.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_FRAME_MAX_SIDE 16384
+#define M324_FRAME_NONE 0
+#define M324_FRAME_THRESHOLD 1
+#define M324_FRAME_SOFT 2
+#define M324_FRAME_BINARY 3
+#define M324_FRAME_AXIS_X 0
+#define M324_FRAME_AXIS_Y 1
+int m324_frame_plan(int in_size, int out_size, int lines, int channels, int frames, long* scratch_bytes);
+int m324_frame_mask(const unsigned char* src, long src_frame, long src_pitch, int src_pixel, const unsigned char* alpha, long alpha_frame,
+                    long alpha_pitch, int alpha_pixel, int frames, int height, int width, int mode, int threshold,
+                    const unsigned char* table, unsigned char* masked, unsigned char* mask, int* boxes, void* stream);
+int m324_frame_resample(const unsigned char* src, long src_frame, long src_pitch, int src_pixel, int src_w, int src_h, int crop_x,
+                        int crop_y, int crop_w, int crop_h, int channels, int frames, int axis, const int* coef, const int* bounds,
+                        int out_size, int ksize, const unsigned char* alpha, long alpha_frame, long alpha_pitch, int alpha_pixel,
+                        int mode, int threshold, const unsigned char* table, unsigned char* dst, long dst_frame, long dst_pitch,
+                        int dst_pixel, int dst_w, int dst_h, int paste_x, int paste_y, int fill, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

@@ -1116,6 +1116,108 @@ def surface_track(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor
     return TrackedSamples(points, normals, colors, face_index, points64)
 
 
+# ------------------------------------------------------------------------------------------------ video framing
+FRAME_MODES = {"none": 0, "threshold": 1, "soft": 2, "binary": 3}          # M324_FRAME_* of include/m324.h
+FRAME_AXES = {"x": 0, "y": 1}
+
+
+def frame_plan(in_size: int, out_size: int, lines: int = 1, channels: int = 3, frames: int = 1):
+    """(ksize, bytes of the pass's result) of one resampling pass: m324_frame_plan, host-only"""
+    need = C.c_long(0)
+    ksize = int(L.load().m324_frame_plan(in_size, out_size, lines, channels, frames, C.addressof(need)))
+    L.check(0 if ksize > 0 else ksize, "m324_frame_plan")
+    return ksize, int(need.value)
+
+
+def _frame_image(t, channels, name: str):
+    """uint8 device image stack [T,H,W,>=channels] (or [T,H,W] for one channel) with a unit channel stride -> (pointer, byte
+    strides of frame / row / pixel, T, H, W); views with a padded pitch or a wider pixel are taken as they are"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if t.dtype != torch.uint8:
+        raise L.M324Error(f"{name}: expected uint8, got {t.dtype}")
+    if t.dim() == 3 and channels == 1:
+        t = t.unsqueeze(-1)
+    if t.dim() != 4 or t.shape[3] < channels or 0 in t.shape or (t.shape[3] > 1 and t.stride(3) != 1) or min(t.stride()[:3]) < 0:
+        raise L.M324Error(f"{name}: expected a non-empty [T,H,W,{channels}] uint8 image stack with a unit channel stride, got {tuple(t.shape)} {t.stride()}")
+    return t.data_ptr(), t.stride(0), t.stride(1), t.stride(2), t.shape[0], t.shape[1], t.shape[2]
+
+
+def _frame_table(table, mode: str, device, name: str):
+    if mode != "soft":
+        return None
+    table = _device_array(table, torch.uint8, f"{name}: table") if table is not None else None
+    if table is None or table.numel() != 65536 or table.device != device:
+        raise L.M324Error(f"{name}: the soft mode needs a uint8 [256,256] table on the video's device")
+    return table
+
+
+def frame_mask(video: torch.Tensor, alpha: Optional[torch.Tensor] = None, *, mode: str = "threshold", threshold: int = 204,
+               table: Optional[torch.Tensor] = None, want_masked: bool = True, want_mask: bool = True):
+    """Masking and per-frame boxes (m324_frame_mask): video uint8 [T,H,W,4] (RGBA) or [T,H,W,3] with alpha [T,H,W] ->
+    (masked [T,H,W,3] or None, mask [T,H,W] or None, boxes int32 [T,4] = (left, top, right, bottom), left >= right on a frame
+    without foreground)."""
+    if mode not in ("threshold", "soft"):
+        raise L.M324Error(f"frame_mask: mode must be 'threshold' or 'soft', got {mode!r}")
+    sp, sf, spitch, spix, T, H, W = _frame_image(video, 3, "frame_mask: video")
+    ap = af = apitch = apix = 0
+    if alpha is None:
+        if video.shape[3] != 4:
+            raise L.M324Error(f"frame_mask: without alpha the video is RGBA [T,H,W,4], got {tuple(video.shape)}")
+        ap = None
+    else:
+        ap, af, apitch, apix, Ta, Ha, Wa = _frame_image(alpha, 1, "frame_mask: alpha")
+        if (Ta, Ha, Wa) != (T, H, W) or alpha.device != video.device:
+            raise L.M324Error(f"frame_mask: alpha {tuple(alpha.shape)} does not match video {tuple(video.shape)}")
+    table = _frame_table(table, mode, video.device, "frame_mask")
+    dev = video.device
+    masked = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_masked else None
+    mask = torch.empty((T, H, W), dtype=torch.uint8, device=dev) if want_mask else None
+    boxes = torch.empty((T, 4), dtype=torch.int32, device=dev)
+    L.check(L.load().m324_frame_mask(sp, sf, spitch, spix, ap, af, apitch, apix, T, H, W, FRAME_MODES[mode], int(threshold), _p(table),
+                                     _p(masked), _p(mask), _p(boxes), _stream()), "m324_frame_mask")
+    _wrote(masked, mask, boxes)
+    return masked, mask, boxes
+
+
+def frame_resample(src: torch.Tensor, coef: torch.Tensor, bounds: torch.Tensor, axis: str, *, channels: int = 3, crop=None,
+                   alpha: Optional[torch.Tensor] = None, mode: str = "none", threshold: int = 204, table: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, paste=(0, 0), fill: int = -1) -> torch.Tensor:
+    """One separable resampling pass (m324_frame_resample) along `axis` ("x" or "y") over the crop (x, y, w, h) of src uint8
+    [T,H,W,channels]; coef int32 [out_size, ksize], bounds int32 [out_size, 2] as framing.resample_tables builds them.  The
+    result goes to a new dense tensor, or is pasted at `paste` = (x, y) into `out`; fill >= 0 writes all of `out`."""
+    if axis not in FRAME_AXES or mode not in FRAME_MODES:
+        raise L.M324Error(f"frame_resample: axis must be 'x' or 'y' and mode one of {sorted(FRAME_MODES)}, got {axis!r}, {mode!r}")
+    sp, sf, spitch, spix, T, H, W = _frame_image(src, channels, "frame_resample: src")
+    cx, cy, cw, ch = (0, 0, W, H) if crop is None else (int(v) for v in crop)
+    coef = _device_array(coef, torch.int32, "frame_resample: coef")
+    bounds = _device_array(bounds, torch.int32, "frame_resample: bounds")
+    if coef.dim() != 2 or 0 in coef.shape or tuple(bounds.shape) != (coef.shape[0], 2):
+        raise L.M324Error(f"frame_resample: expected coef [out,ksize] and bounds [out,2], got {tuple(coef.shape)} / {tuple(bounds.shape)}")
+    out_size, ksize = coef.shape
+    ap = af = apitch = apix = 0
+    if mode == "none":
+        ap = None
+    else:
+        if alpha is None:
+            raise L.M324Error(f"frame_resample: mode {mode!r} needs alpha")
+        ap, af, apitch, apix, Ta, Ha, Wa = _frame_image(alpha, 1, "frame_resample: alpha")
+        if (Ta, Ha, Wa) != (T, H, W):
+            raise L.M324Error(f"frame_resample: alpha {tuple(alpha.shape)} does not match src {tuple(src.shape)}")
+    table = _frame_table(table, mode, src.device, "frame_resample")
+    if out is None:
+        shape = (T, ch, out_size) if axis == "x" else (T, out_size, cw)
+        out = torch.empty(shape + (channels,), dtype=torch.uint8, device=src.device)
+    dp, df, dpitch, dpix, Td, Hd, Wd = _frame_image(out, channels, "frame_resample: out")
+    if Td != T or any(t.device != src.device for t in (coef, bounds, out) + (() if alpha is None else (alpha,))):
+        raise L.M324Error("frame_resample: out has another frame count, or the tensors live on different devices")
+    L.check(L.load().m324_frame_resample(sp, sf, spitch, spix, W, H, cx, cy, cw, ch, channels, T, FRAME_AXES[axis], _p(coef), _p(bounds), out_size,
+                                         ksize, ap, af, apitch, apix, FRAME_MODES[mode], int(threshold), _p(table), dp, df, dpitch, dpix, Wd, Hd,
+                                         int(paste[0]), int(paste[1]), int(fill), _stream()), "m324_frame_resample")
+    _wrote(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
