@@ -446,6 +446,18 @@ def point_encode(proj, ref, out_dtype=torch.bfloat16):
     return _round_out(ref, e, out_dtype)
 
 
+def linear_n3(a, w, bias):
+    """m324_linear_n3 (linear_n3_kernel, motion324_amd/csrc/elementwise.hip): out[M, 3] fp32 = a w^T + bias, a [M, K] the values
+    the kernel reads, w [3, K], bias [3].  The longest chain of roundings a product passes through: the four-term dot of one step
+    (4: its product and three additions), the lane's running sum over ceil(K / 256) steps, the six butterfly levels of wave_sum
+    (motion324_amd/csrc/common.h), the bias addition: (4 + ceil(K / 256) + 6 + 1) U32 (|a| |w|^T + |bias|).  The order is
+    known, so the factor 2 of the MFMA sums is not applied; contraction into FMAs only removes roundings.  The output is fp32 and
+    the last rounding is the bias addition's: no further term."""
+    a, w, bias = _f64(a), _f64(w), _f64(bias)
+    K = a.shape[1]
+    return (4 + -(-K // 256) + 6 + 1) * U32 * (a.abs() @ w.abs().T + bias.abs())
+
+
 # ------------------------------------------------------------------------------------------- optimizer step (fp32 throughout)
 TINY32 = 2.0 ** -126       # smallest normal fp32: what one operation loses at most when its result (or an operand) is flushed to zero
 
