@@ -566,3 +566,232 @@ def sum_of_squares(total, n, depth, *, term_roundings=1, post_roundings=0):
     additions (sum_depth), and post_roundings further operations scale the result.  Non-negative terms: the relative errors add,
     gamma_k total; n TINY32 for squares that underflow."""
     return _gamma(depth + term_roundings + post_roundings) * float(total) + n * TINY32
+
+
+# ------------------------------------------------------------------------------------------- row, reduction and layout kernels
+def _two_pass_stats(x, eps):
+    """row_stats (motion324_amd/csrc/elementwise.hip): fp32 two-pass mean / rstd of a row held in registers.  Returns the fp64
+    values and what the fp32 evaluation may be off by: mean, xc = x - mean, var, rstd and their errors dm, dxc, drstd.
+    The sums over C run in an undocumented order across lanes and butterfly levels: gamma_C with the factor 2.  Unlike `layernorm`
+    the variance keeps its second-order term mean(dxc^2) (on a constant row it is all there is: the exact variance is 0 and the
+    computed one is the square of the mean's error), and the rsqrt is bounded by its exact form 1 / sqrt(1 - t) - 1 for a
+    relative error t of its argument, not by the tangent t / 2."""
+    C = x.shape[-1]
+    g = 2 * (C + 2) * U32
+    mean = x.mean(-1, keepdim=True)
+    xc = x - mean
+    var = (xc * xc).mean(-1, keepdim=True)
+    dm = g * x.abs().mean(-1, keepdim=True)
+    dxc = dm + U32 * xc.abs()
+    sq = ((xc.abs() + dxc) ** 2).mean(-1, keepdim=True)               # what the squares may sum to
+    dvar = (2 * xc.abs() * dxc + dxc * dxc).mean(-1, keepdim=True) + (g + 2 * U32) * sq + U32 * (sq + eps)
+    t = dvar / (var + eps)
+    assert float(t.max()) < 0.5, "row statistics: the variance is not known to within half of var + eps"
+    rstd = 1.0 / torch.sqrt(var + eps)
+    drstd = rstd * ((1.0 / torch.sqrt(1 - t) - 1) * (1 + EXP2) + EXP2)
+    return mean, xc, var, rstd, dm, dxc, drstd
+
+
+def rowstats(x, eps):
+    """m324_rowstats (rowstats_kernel): rowstat[m] = (rstd, -rstd mean) by the two-pass statistics.  Returns the two bounds
+    [rows] separately: an error of rstd scales every output of the folded consumer, one of -rstd mean shifts it."""
+    x = _f64(x)
+    mean, _, _, rstd, dm, _, drstd = _two_pass_stats(x, eps)
+    b1 = drstd * mean.abs() + (rstd + drstd) * dm + 2 * U32 * (rstd * mean).abs()
+    return drstd[:, 0], b1[:, 0]
+
+
+def rowstats_finish_reference(part, eps):
+    """fp64 statement of m324_rowstats_finish: part [ncb, M, 2] = (sum, M2) of blocks of 64 values -> (rstd, -rstd mean) [M]"""
+    part = _f64(part)
+    ncb = part.shape[0]
+    n = 64.0 * ncb
+    mean = part[..., 0].sum(0) / n
+    m2 = part[..., 1].sum(0) + 64.0 * ((part[..., 0] / 64.0 - mean) ** 2).sum(0)
+    rstd = 1.0 / torch.sqrt(m2 / n + eps)
+    return rstd, -rstd * mean
+
+
+def rowstats_finish(part, eps):
+    """m324_rowstats_finish (rowstats_finish_kernel): one thread per row, every operation in the order written, so the bound is a
+    running error analysis of that code and the factor 2 of the undocumented orders is not applied (as in linear_n3); contraction
+    of a product and a sum into an FMA only removes roundings.  Even ncb: each half of the blocks by Chan's update (d = mean_b -
+    mean; mean += d / (i + 1); M2 += d^2 64 i / (i + 1) + M2_b), then ln_combine_halves' pairwise form.  Odd ncb: the sum of the
+    block sums, then M2 = sum (64 d^2 + M2_b).  e_x below is the absolute error of the computed x.  Returns (b_rstd, b_-rstd mean)."""
+    part = _f64(part)
+    ncb, M, _ = part.shape
+    u = U32
+    sx, sy = part[..., 0], part[..., 1]
+    n = 64.0 * ncb
+    if ncb % 2 == 0:
+        h = ncb // 2
+        mean, m2, e_mean, e_m2 = [], [], [], []
+        for half in range(2):
+            mu, q = sx[half * h] / 64.0, sy[half * h].clone()
+            e_mu, e_q = torch.zeros(M, dtype=torch.float64), torch.zeros(M, dtype=torch.float64)
+            for i in range(1, h):
+                d = sx[half * h + i] / 64.0 - mu
+                e_d = e_mu + u * d.abs()
+                mu = mu + d / (i + 1)
+                e_mu = e_mu + (e_d + u * (d.abs() + e_d)) / (i + 1) + u * (mu.abs() + e_mu + e_d)     # 1 / (i + 1) rounded; the fma
+                coef = 64.0 * i / (i + 1)
+                T = coef * d * d
+                e_T = coef * (2 * d.abs() * e_d + e_d * e_d) + 2 * u * (T + coef * (2 * d.abs() * e_d + e_d * e_d))   # d d, the coefficient
+                inner = T + sy[half * h + i]
+                e_in = e_T + u * (inner.abs() + e_T)
+                q = q + inner
+                e_q = e_q + e_in + u * (q.abs() + e_q + e_in)
+            mean.append(mu), m2.append(q), e_mean.append(e_mu), e_m2.append(e_q)
+        d = mean[1] - mean[0]
+        e_d = e_mean[0] + e_mean[1] + u * d.abs()
+        ssum = m2[0] + m2[1]
+        e_s = e_m2[0] + e_m2[1] + u * (ssum.abs() + e_m2[0] + e_m2[1])
+        T = 32.0 * h * d * d
+        e_T = 32.0 * h * (2 * d.abs() * e_d + e_d * e_d)
+        e_T = e_T + 2 * u * (T + e_T)
+        mm2 = ssum + T
+        e_mm2 = e_s + e_T + u * (mm2.abs() + e_s + e_T)
+        mu = mean[0] + 0.5 * d
+        e_mu = e_mean[0] + 0.5 * e_d + u * (mu.abs() + e_mean[0] + e_d)
+    else:
+        s = sx.sum(0)
+        e_s = _gamma(ncb) * sx.abs().sum(0)
+        mu = s / n
+        e_mu = e_s / n + u * (mu.abs() + e_s / n)
+        d = sx / 64.0 - mu
+        e_d = e_mu + u * d.abs()
+        term = 64.0 * d * d + sy
+        e_t = 64.0 * (2 * d.abs() * e_d + e_d * e_d)
+        e_t = e_t + u * (term.abs() + e_t)
+        mm2 = term.sum(0)
+        e_mm2 = e_t.sum(0) + _gamma(ncb) * (term.abs() + e_t).sum(0)
+    var = mm2 / n
+    dvar = e_mm2 / n + u * (var.abs() + e_mm2 / n)                       # the division
+    dvar = dvar + u * (var.abs() + eps + dvar)                          # + eps
+    t = dvar / (var + eps)
+    assert float(t.max()) < 0.5, "rowstats_finish: the variance is not known to within half of var + eps"
+    rstd = 1.0 / torch.sqrt(var + eps)
+    drstd = rstd * ((1.0 / torch.sqrt(1 - t) - 1) * (1 + EXP2) + EXP2)
+    b1 = drstd * mu.abs() + (rstd + drstd) * e_mu + 2 * u * (rstd * mu).abs()
+    return drstd, b1
+
+
+def layernorm_backward_reference(x, w, eps, dy, addend=None):
+    """fp64 statement of m324_layernorm_bwd on compact rows: (dx (+ addend), dw, db)"""
+    x, w, dy = _f64(x), _f64(w), _f64(dy)
+    mean = x.mean(-1, keepdim=True)
+    xc = x - mean
+    rstd = 1.0 / torch.sqrt((xc * xc).mean(-1, keepdim=True) + eps)
+    xh = xc * rstd
+    g = dy * w
+    dx = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+    if addend is not None:
+        dx = dx + _f64(addend)
+    return dx, (dy * xh).sum(0), dy.sum(0)
+
+
+def layernorm_backward(x, w, eps, dy, addend=None):
+    """m324_layernorm_bwd / _bwd_cast (layernorm_bwd_kernel, motion324_amd/csrc/elementwise.hip: "xh = (x - mean) * rstd ; g = dy * w ;
+    dx += rstd * (g - mean(g) - xh * mean(g * xh))"), fp32 on exact operands x [rows, C], dy [rows, C] (compact rows: the caller
+    maps them), in the style of rmsnorm_heads_backward.  Statistics as in `rowstats`; xh carries them and two products; the two
+    row means are sums over C in an undocumented order (gamma_C with the factor 2); three operations inside the bracket, the
+    product with rstd, then the accumulate addend and the fp32 store (2 U32 of the stored value).  dw = sum_rows dy xh and db =
+    sum_rows dy pass the wave's running sum, the eight waves' sum through LDS and m324_colsum's levels: the rows in any order,
+    gamma_rows with the factor 2.  Returns (b_dx [rows, C], b_dw [C], b_db [C])."""
+    x, w, dy = _f64(x), _f64(w), _f64(dy)
+    rows, C = x.shape
+    gC = 2 * (C + 2) * U32
+    _, xc, _, rstd, _, dxc, drstd = _two_pass_stats(x, eps)
+    xh = xc * rstd
+    e_xh = dxc * rstd + (xc.abs() + dxc) * drstd + 2 * U32 * xh.abs()
+    g = dy * w
+    e_g = U32 * g.abs()
+    s1 = g.mean(-1, keepdim=True)
+    e_s1 = (gC + U32) * g.abs().mean(-1, keepdim=True)
+    s2 = (g * xh).mean(-1, keepdim=True)
+    e_s2 = ((g.abs() + e_g) * e_xh).mean(-1, keepdim=True) + (gC + 2 * U32) * (g * xh).abs().mean(-1, keepdim=True)
+    inner = g - s1 - xh * s2
+    e_in = e_g + e_s1 + xh.abs() * e_s2 + (s2.abs() + e_s2) * e_xh + 3 * U32 * (g.abs() + s1.abs() + (xh * s2).abs())
+    val = rstd * inner
+    e = rstd * e_in + drstd * (inner.abs() + e_in) + U32 * val.abs()
+    if addend is not None:
+        val = val + _f64(addend)
+    gR = 2 * (rows + 2) * U32
+    b_dw = (dy.abs() * e_xh).sum(0) + gR * (dy * xh).abs().sum(0)
+    b_db = gR * dy.abs().sum(0)
+    return _round_out(val, e, torch.float32), b_dw, b_db
+
+
+def colsum_plan(rows, cols, ld, aligned16=True, scratch_rows=0):
+    """(kernel, depth) of m324_colsum -- the host conditions of the entry point (motion324_amd/csrc/elementwise.hip, m324_colsum)
+    and the longest chain of fp32 additions a term passes through in the kernel it selects:
+      wide / wide4   (rows <= 64): one thread walks the rows: rows
+      plain          (65 .. 255 rows, or no scratch): wave w takes rows w, w + 4, ...: ceil(rows / 4), then red[0] + .. + red[3]: 3
+      two-stage      (rows >= 256 with scratch): chunk k of R = min(scratch_rows, 256) takes rows 4 k + w, step 4 R:
+                     ceil(rows / (4 R)) + 3, then the wide kernel over the R partial rows: R"""
+    v4 = cols % 4 == 0 and ld % 4 == 0 and aligned16
+    if scratch_rows > 1 and rows >= 256:
+        R = min(scratch_rows, 256)
+        return ("colsum_chunk4 + colsum_wide4" if v4 else "colsum_chunk + colsum_wide"), -(-rows // (4 * R)) + 3 + R
+    if rows <= 64:
+        return ("colsum_wide4" if v4 else "colsum_wide"), rows
+    return "colsum", -(-rows // 4) + 3
+
+
+def colsum_multi_depth(rows_of_chain):
+    """longest chain of additions of one destination of m324_colsum_multi (colsum_multi_kernel): a chain with a source of more than
+    64 rows takes the tall path for every item -- wave w of 16 walks rows w, w + 16, ..., the sixteen sums are added in order:
+    ceil(rows / 16) + 15 -- any other chain the row walk of colsum_wide: rows; every item after the first adds once more."""
+    tall = any(r > 64 for r in rows_of_chain)
+    return max((-(-r // 16) + 15) if tall else r for r in rows_of_chain) + len(rows_of_chain) - 1
+
+
+def colsum(x, depth, addend=None):
+    """m324_colsum / m324_colsum_multi: out[c] (+)= sum_r x[r][c] -- a sum of exact terms in the kernel's own order, so no factor 2:
+    gamma_depth sum |x| with depth from colsum_plan / colsum_multi_depth, plus the rounding of the accumulate addition.
+    x [rows, cols]: the values the kernel reads (a list of tensors: the items of a chain)."""
+    xs = [_f64(t) for t in (x if isinstance(x, (list, tuple)) else [x])]
+    total = sum(t.sum(0) for t in xs)
+    e = _gamma(depth) * sum(t.abs().sum(0) for t in xs)
+    if addend is not None:
+        e = e + U32 * ((total + _f64(addend)).abs() + e)
+    return e
+
+
+def attention_delta(o, do):
+    """m324_attention_delta (attn_delta_kernel, motion324_amd/csrc/backward.hip): D = sum over a head's 64 columns of O dO, exact
+    operands [..., 64].  A 64-term dot product in a known order: the product (1), the lane's eight additions, the three xor-shuffle
+    levels of group8_sum: gamma_12 sum |O dO|."""
+    o, do = _f64(o), _f64(do)
+    return _gamma(12) * (o * do).abs().sum(-1)
+
+
+def rmsnorm_weight_grad(x, dy, eps):
+    """weight gradient of the per-head RMSNorm (qkv_split_bwd_kernel + m324_colsum): dw[c] = sum over the (token, head) rows of
+    dy xh, xh = x r.  xh carries r's relative (n + 2) U32 + EXP2 and one product; the rows are added per lane, across the eight
+    rows of a wave, the four waves, the workgroups' partials (m324_colsum): any order, gamma_rows with the factor 2.
+    x, dy [rows, 64]."""
+    x, dy = _f64(x), _f64(dy)
+    rows, n = x.shape
+    r = torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
+    t = (dy * x * r).abs().sum(0)
+    return ((n + 2) * U32 + EXP2 + 2 * U32 + 2 * (rows + 2) * U32) * t
+
+
+def merge_parts(parts, lses, out_dtype=torch.bfloat16):
+    """m324_attention_merge on GIVEN parts (attention_merge_kernel, motion324_amd/csrc/elementwise.hip): O = sum_i w_i O_i,
+    w_i = 2^(l_i - m) / sum_j 2^(l_j - m), exact operands O_i [rows, H 64] and l_i [B, H, Lq] (fp32, log2 domain).  Each weight
+    carries the rounding of l_i - m (U32 |l_i - m| ln 2 on the weight), one exp2, the sum of the weights, the reciprocal and a
+    product -- twice, for the numerator and the normalisation, as in attention_merge: 2 ln 2 U32 max|l_i - m| + 2 EXP2 +
+    2 (n + 2) U32 -- then the fp32 sum over the parts and one output rounding.  Returns (fp64 reference, bound)."""
+    parts, lses = [_f64(p) for p in parts], [_f64(l) for l in lses]
+    B, H, Lq = lses[0].shape
+    tok = lambda t: t.permute(0, 2, 1).reshape(B * Lq, H, 1).expand(-1, -1, 64).reshape(B * Lq, H * 64)
+    m = torch.stack(lses).max(0).values
+    w = [torch.exp2(l - m) for l in lses]
+    tot = sum(w)
+    gap = torch.stack([(l - m).abs() for l in lses]).max(0).values
+    drel = tok(2 * LN2 * U32 * gap + 2 * EXP2 + 2 * (len(parts) + 2) * U32)
+    val = sum(tok(wi / tot) * p for wi, p in zip(w, parts))
+    mag = sum(tok(wi / tot) * p.abs() for wi, p in zip(w, parts))
+    return val, _round_out(val, drel * mag, out_dtype)

@@ -16,6 +16,7 @@ import torch
 
 import error_bounds as eb
 import optimizer_cases as oc
+import rowkernel_cases as rc
 from conftest import rel_err
 
 BF = torch.bfloat16
@@ -705,3 +706,169 @@ def test_sum_of_squares_bound_and_plans():
     bound = eb.sum_of_squares(want, n, depth)
     assert abs(float(fin[0]) - want) <= bound < 1e-5 * want / 4
     assert abs(float(np.float32(want * (1 + 3e-6))) - want) > bound          # a sum that is off by 3e-6 passed the old gate
+
+
+# ------------------------------------------------------------------------------------------- row, reduction and layout kernels
+def _within(out, ref, bound, what):
+    return eb.assert_within(out, ref, bound, what)
+
+
+@pytest.mark.parametrize("C", rc.LN_WIDTHS)
+def test_layernorm_and_rowstats_bounds_are_sound_over_the_case_table(C):
+    """fp32 emulation (torch's summation order) of every width, with the special rows, fp32 and bf16 inputs"""
+    for rows in rc.LN_ROWS:
+        w, b = rc.ln_params(C)
+        for xdt in (torch.float32, BF):
+            x = rc.ln_input(rows, C, dtype=xdt).float()
+            for odt, bias, eps in rc.LN_VARIANTS:
+                bb = b if bias else None
+                _within(rc.emu_layernorm(x, w, bb, eps, odt), rc.ln_reference(x, w, bb, eps), eb.layernorm(x, w, bb, eps, out_dtype=odt),
+                        f"layernorm emulation C={C} rows={rows} {odt} bias={bias} eps={eps}")
+            for eps in (1e-5, 1e-6):
+                got, ref, bnd = rc.emu_rowstats(x, eps), rc.rowstats_reference(x, eps), eb.rowstats(x, eps)
+                for k, name in enumerate(("rstd", "-rstd mean")):
+                    _within(got[k], ref[k], bnd[k], f"rowstats emulation {name} C={C} rows={rows} eps={eps}")
+
+
+@pytest.mark.parametrize("ncb", rc.FINISH_NCB)
+def test_rowstats_finish_bound_is_sound(ncb):
+    for M in rc.FINISH_M:
+        for eps in (1e-5, 1e-6):
+            part = rc.finish_table(ncb, M)
+            got, ref, bnd = rc.emu_rowstats_finish(part, eps), eb.rowstats_finish_reference(part, eps), eb.rowstats_finish(part, eps)
+            for k, name in enumerate(("rstd", "-rstd mean")):
+                _within(got[k], ref[k], bnd[k], f"rowstats_finish emulation {name} ncb={ncb} M={M}")
+            # the bounds still test something: 1e-4 of rstd, and of -rstd mean measured against sqrt((rstd mean)^2 + 1)
+            assert float((bnd[0] / ref[0]).max()) < 1e-4 and float((bnd[1] / (ref[1] ** 2 + 1).sqrt()).max()) < 1e-4
+
+
+@pytest.mark.parametrize("i", [1, 3, 7])
+def test_chan_block_merged_with_the_wrong_weight_leaves_the_bound(i):
+    """block i of the first half merged with weight 64 in place of 64 i / (i + 1): M2 grows by 64 d^2 / (i + 1)"""
+    part = rc.finish_table(16, 257)
+    bad = rc.emu_rowstats_finish(part, 1e-5, wrong_weight_block=i)
+    ref, bnd = eb.rowstats_finish_reference(part, 1e-5), eb.rowstats_finish(part, 1e-5)
+    hit = eb.violations(bad[0], ref[0], bnd[0])
+    m = torch.arange(257)
+    assert float(hit[m % 4 == 1].double().mean()) > 0.9 and int(hit.sum()) > 128    # nearly every row whose block means differ, and most others
+
+
+@pytest.mark.parametrize("C", rc.BWD_WIDTHS)
+def test_layernorm_backward_bound_is_sound(C):
+    for rows in rc.BWD_ROWS:
+        w, _ = rc.ln_params(C)
+        x = rc.ln_input(rows, C)
+        for dt in (torch.float32, BF):
+            dy = _q(_rand((rows, C), 77 + C), dt)
+            for addend in (None, _rand((rows, C), 78 + C)):
+                got = rc.emu_layernorm_bwd(x, w, 1e-5, dy, addend)
+                ref = eb.layernorm_backward_reference(x, w, 1e-5, dy, addend)
+                bnd = eb.layernorm_backward(x, w, 1e-5, dy, addend)
+                for k, name in enumerate(("dx", "dw", "db")):
+                    _within(got[k], ref[k], bnd[k], f"layernorm backward emulation {name} C={C} rows={rows} {dt}")
+
+
+def test_one_rows_dw_contribution_dropped_leaves_the_bound():
+    C, rows = 260, 70
+    w, _ = rc.ln_params(C)
+    x, dy = rc.ln_input(rows, C), _rand((rows, C), 79)
+    ref, bnd = eb.layernorm_backward_reference(x, w, 1e-5, dy), eb.layernorm_backward(x, w, 1e-5, dy)
+    for row in (0, 33, 69):
+        bad = rc.emu_layernorm_bwd(x, w, 1e-5, dy, drop_dw_row=row)
+        assert int(eb.violations(bad[1], ref[1], bnd[1]).sum()) >= 0.9 * C, row      # every column but those where the row's term is small by chance
+        assert not bool(eb.violations(bad[0], ref[0], bnd[0]).any()) and not bool(eb.violations(bad[2], ref[2], bnd[2]).any())
+
+
+def test_skipped_slot_in_the_statistics_passes_the_norm_gate_but_not_the_bound():
+    """columns 256 i + 4 lane .. + 3 of ONE row missing from the row's two sums (an `if (c < C)` that skips a partly filled slot): at
+    the existing test's shape, 77 x 768 with a bf16 output, the Frobenius-norm ratio stays below that test's 4e-3 gate"""
+    rows, C, eps = 77, 768, 1e-5
+    x = _rand((rows, C), 11) * 3 + 0.5
+    w, _ = rc.ln_params(C)
+    ref = rc.ln_reference(x, w, None, eps)
+    for slot, lane in ((0, 0), (1, 63), (2, 17)):
+        skip = (40, 256 * slot + 4 * lane)
+        bad = rc.emu_layernorm(x, w, None, eps, BF, skip=skip)
+        assert rel_err(bad.float(), ref) < 4e-3
+        hit = eb.violations(bad, ref, eb.layernorm(x, w, None, eps))
+        assert bool(hit[40].any()) and not bool(hit[:40].any()) and not bool(hit[41:].any())
+        st, sref, sb = rc.emu_rowstats(x, eps, skip=skip), rc.rowstats_reference(x, eps), eb.rowstats(x, eps)
+        assert bool(eb.violations(st[1], sref[1], sb[1])[40]) and int(eb.violations(st[1], sref[1], sb[1]).sum()) == 1
+    # the widths of the new cases: the last, partly filled slot
+    for C in (260, 1000):
+        x, (w, _) = rc.ln_input(17, C), rc.ln_params(C)
+        skip = (5, C - 4)
+        bad = rc.emu_layernorm(x, w, None, eps, torch.float32, skip=skip)
+        hit = eb.violations(bad, rc.ln_reference(x, w, None, eps), eb.layernorm(x, w, None, eps, out_dtype=torch.float32))
+        assert bool(hit[5].any()) and int(hit.any(-1).sum()) == 1
+
+
+def test_lone_last_row_left_unwritten_leaves_the_bound():
+    C, rows = 260, 9
+    x, (w, b) = rc.ln_input(rows, C), rc.ln_params(C)
+    out = torch.full((rows, C), float("nan"))
+    out[:8] = rc.emu_layernorm(x, w, b, 1e-5, torch.float32)[:8]
+    hit = eb.violations(out, rc.ln_reference(x, w, b, 1e-5), eb.layernorm(x, w, b, 1e-5, out_dtype=torch.float32))
+    assert bool(hit[8].all()) and not bool(hit[:8].any())
+    stale = out.clone()
+    stale[8] = out[7]                                                      # or holding its neighbour's values
+    hit = eb.violations(stale, rc.ln_reference(x, w, b, 1e-5), eb.layernorm(x, w, b, 1e-5, out_dtype=torch.float32))
+    assert int(hit[8].sum()) > C - 8
+
+
+@pytest.mark.parametrize("case,kernel", rc.COLSUM_CASES)
+def test_colsum_bound_is_sound_and_rejects_a_group_taken_from_its_neighbour(case, kernel):
+    rows, cols, ld, voff = case
+    name, depth = eb.colsum_plan(rows, cols, ld, aligned16=(voff == 0), scratch_rows=rc.colsum_scratch_rows(rows))
+    assert name == kernel
+    for dt in (torch.float32, BF):
+        _, x = rc.colsum_input(rows, cols, ld, voff, dt)
+        addend = _rand((cols,), 80)
+        for add in (None, addend):
+            got = rc.emu_colsum(x, 4 if kernel == "colsum" else 1)
+            ref = x.double().sum(0)
+            if add is not None:
+                got, ref = add + got, ref + add.double()
+            bnd = eb.colsum(x, depth, add)
+            _within(got, ref, bnd, f"colsum emulation {case} {dt}")
+            bad = got.clone()
+            c0 = (cols // 4 // 2) * 4 + 4 if cols >= 12 else 4
+            bad[c0:c0 + 4] = got[c0 - 4:c0]
+            assert int(eb.violations(bad, ref, bnd).sum()) >= min(4, cols - c0) - 1, case
+
+
+def test_colsum_multi_depth_attention_delta_and_rmsnorm_weight_grad_bounds():
+    assert eb.colsum_multi_depth([5, 5, 5]) == 7 and eb.colsum_multi_depth([65]) == 20 and eb.colsum_multi_depth([700, 3]) == 44 + 15 + 1
+    for B, H, L in rc.DELTA_SHAPES:
+        for dt in (torch.float32, BF):
+            o, do = _q(_rand((B * L, H, 64), 81), dt), _q(_rand((B * L, H, 64), 82), dt)
+            _within((o * do).sum(-1), (o.double() * do.double()).sum(-1), eb.attention_delta(o, do), f"delta emulation {(B, H, L)} {dt}")
+    x, dy = _q(_rand((520, 64), 83)), _q(_rand((520, 64), 84))
+    r = torch.rsqrt((x * x).mean(-1, keepdim=True) + 1e-5)
+    _, dw = rc.rmsnorm_backward_reference(x, dy, torch.ones(64), 1e-5)
+    _within((dy * (x * r)).sum(0), dw, eb.rmsnorm_weight_grad(x, dy, 1e-5), "rmsnorm weight gradient emulation")
+    drop = (dy * (x * r))[1:].sum(0)
+    assert int(eb.violations(drop, dw, eb.rmsnorm_weight_grad(x, dy, 1e-5)).sum()) >= 56
+
+
+@pytest.mark.parametrize("gap", [0.0, 30.0])
+@pytest.mark.parametrize("n_parts", [2, 3])
+def test_merge_parts_bound_is_sound_and_rejects_a_part_weighted_as_its_neighbour(gap, n_parts):
+    """fp32 emulation of attention_merge_kernel on synthetic parts; the fault: the last part enters with the first part's weight"""
+    B, H, Lq = rc.MERGE_SHAPES[1]
+    tok = lambda t: t.permute(0, 2, 1).reshape(B * Lq, H, 1).expand(-1, -1, 64).reshape(B * Lq, H * 64)
+    for dt in (torch.float32, BF):
+        parts = [_q(_rand((B * Lq, H * 64), 130 + i), dt) for i in range(n_parts)]
+        base = _rand((B, H, Lq), 135, 3.0)
+        lses = [base + 0.0, base - gap] + ([base - gap] if n_parts == 3 else [])
+        ref, bound = eb.merge_parts(parts, lses, out_dtype=dt)
+        m = torch.stack(lses).max(0).values
+        w = [torch.exp2(l - m) for l in lses]
+        inv = 1.0 / sum(w)
+        out = sum(tok(wi * inv) * p for wi, p in zip(w, parts)).to(dt).float()
+        eb.assert_within(out, ref, bound, f"merge emulation gap={gap} parts={n_parts} {dt}")
+        if gap:
+            w[-1] = w[0]
+            inv = 1.0 / sum(w)
+            bad = sum(tok(wi * inv) * p for wi, p in zip(w, parts)).to(dt).float()
+            assert float(eb.violations(bad, ref, bound).double().mean()) > 0.95
