@@ -523,6 +523,73 @@ int m324_frame_resample(const unsigned char* src, long src_frame, long src_pitch
                         int mode, int threshold, const unsigned char* table, unsigned char* dst, long dst_frame, long dst_pitch,
                         int dst_pixel, int dst_w, int dst_h, int paste_x, int paste_y, int fill, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh clip rendering (csrc/render.hip; added at ABI 23 without a bump): an orthographic, z-buffered rasterizer over `frames`
+ * poses of one topology, and shaded frames with face-id and depth buffers.  replaces: nothing the reference runs on this
+ * hardware (it renders through Blender, utils/render.py; its one rasterizer is CUDA).  The arithmetic below IS the contract:
+ * which triangle owns a pixel is decided in integers and settled by a 64-bit atomic min, which commutes, so no output depends on
+ * arrival order, grid, CU count, queue order or big_pixels.  All fp32 arithmetic is evaluated as written, without contraction
+ * (fl(a * b + c) never fuses), with correctly rounded division and square root.
+ *
+ * Sizes: size = S, the image side, 1 <= S <= M324_RENDER_MAX_SIDE; frames >= 1; n_vertices >= 1; n_faces >= 0;
+ *   frames * n_faces < 2^31 and frames * n_vertices < 2^31.  vertices fp32, frame t at vertices + t * stride_t (ELEMENTS), vertex v
+ *   at + 3 v.  faces int32 [n_faces, 3], shared by every frame; a face with an index outside [0, n_vertices) draws nothing (the
+ *   Python wrappers refuse such faces before any launch).  view: 12 floats in HOST memory, the row-major 3 x 4 matrix M.
+ *   The three launch entry points share one scratch buffer (device memory, 16-byte aligned, m324_render_plan bytes for the same
+ *   n_vertices, n_faces, frames, size) and run in the order project, raster, shade on one stream.
+ *
+ * Projection (m324_render_project), per frame and vertex (x, y, z):
+ *   p_r = ((M[r][0] * x + M[r][1] * y) + M[r][2] * z) + M[r][3], r = 0, 1, 2 (the view-space position, kept for shading).
+ *   If p_0, p_1, p_2 are all finite:
+ *     x_sub = rint(clamp((p_0 + 0.5f) * (float)(16 S), -131072, 131072))      1/16 pixel, x to the right
+ *     y_sub = rint(clamp((0.5f - p_1) * (float)(16 S), -131072, 131072))      row 0 is the top
+ *     z_q   = rint(clamp((1.0f - p_2) * 4194304.0f, 0, 8388607))              smaller is nearer: the camera sits on +z, looks to -z
+ *   with clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v) and rint = round to nearest, ties to even.  Otherwise the vertex is
+ *   invalid and every triangle that touches it is skipped.  View space shows the cube [-0.5, 0.5]^2 of x, y and z in [-1, 1].
+ *
+ * Coverage (m324_render_raster).  Triangle f with vertices 0, 1, 2 at integer (x_i, y_i, z_i), all in int64:
+ *   area2 = (x_1 - x_0) * (y_2 - y_0) - (x_2 - x_0) * (y_1 - y_0); area2 = 0: skipped.  s = sign(area2); no back-face culling.
+ *   Edge i, with j = (i + 1) mod 3, k = (i + 2) mod 3:  A_i = s * (y_j - y_k), B_i = s * (x_k - x_j),
+ *     C_i = -s * ((y_j - y_k) * x_j + (x_k - x_j) * y_j),  w_i(X, Y) = A_i * X + B_i * Y + C_i.
+ *   w_i >= 0 inside, and w_0 + w_1 + w_2 = |area2| at every point.  Pixel (px, py) is sampled at (X, Y) = (16 px + 8, 16 py + 8);
+ *   it is covered iff for i = 0, 1, 2:  w_i > 0, or w_i = 0 and (A_i > 0, or A_i = 0 and B_i > 0)  -- the top-left rule without
+ *   reference to the winding: a centre exactly on an edge belongs to the triangle whose interior lies toward +x, on a horizontal
+ *   edge toward +y, so two triangles sharing an edge never both own and never both drop a pixel on it.
+ *   Bounds: |x_i - x_j| <= 2^18, |area2| <= 2^37, sum w_i * z_i <= 2^60: this is where S <= 1024 comes from.
+ * Depth and ownership:  z_pix = (w_0 * z_0 + w_1 * z_1 + w_2 * z_2) / |area2| (int64 division, every term non-negative);
+ *   key = (z_pix << 32) | f.  A pixel's final key is the minimum over the triangles that cover it: the nearest one, the lower face
+ *   index at equal z_pix; all ones = background.
+ * Work distribution (never visible in the result): pixels px with 16 px + 8 inside [min x_i, max x_i], clipped to [0, S - 1],
+ *   and the same for py, form the triangle's box.  An empty box draws nothing.  A box of at most big_pixels (>= 0) pixels is
+ *   walked by the lane that loaded the triangle; the others are appended to a queue of capacity frames * n_faces (one counter
+ *   add per wave) and a second launch gives each entry a whole workgroup, lanes striding over the box.  No workgroup waits for
+ *   another; every loop is bounded by a clipped box or by the queue's capacity.
+ *
+ * Resolve and shade (m324_render_shade), per pixel.  Background: face = -1, depth = -1, rgb = background (0xBBGGRR: red in the
+ *   low byte).  Otherwise face = f, depth = z_pix, and with w_i recomputed for face f at the pixel:
+ *   b_i = (float)w_i / (float)|area2| (int64 to fp32 rounded to nearest even, then one correctly rounded division);
+ *   albedo_c = (b_0 * col_0c + b_1 * col_1c) + b_2 * col_2c from colors (fp32 [n_vertices, 3], device), 0.8f when colors is NULL;
+ *   normal n, flat (normals NULL): e1 = p(1) - p(0), e2 = p(2) - p(0) on the view-space positions,
+ *     n = (e1_y * e2_z - e1_z * e2_y,  e1_z * e2_x - e1_x * e2_z,  e1_x * e2_y - e1_y * e2_x);
+ *   smooth (normals fp32, frame t at normals + t * normal_stride_t ELEMENTS, vertex v at + 3 v):
+ *     m_c = (b_0 * N_0c + b_1 * N_1c) + b_2 * N_2c in model space, then n_r = (M[r][0] * m_0 + M[r][1] * m_1) + M[r][2] * m_2;
+ *   len = sqrt((n_0 * n_0 + n_1 * n_1) + n_2 * n_2);  l = |n_2| / len, and l = 0 unless 0 < len < inf (two-sided, lit from the camera);
+ *   shade = ambient + (1.0f - ambient) * l, ambient in [0, 1];  v = albedo_c * shade;  v = v > 0 ? v : 0 (a NaN counts as 0);
+ *   v = v < 1 ? v : 1;  byte = (int)floor(v * 255.0f + 0.5f).
+ *   Outputs, each skipped when NULL (not all three): rgb uint8 [frames, S, S, 3], face int32 [frames, S, S], depth int32 [frames, S, S].
+ * m324_render_plan: host-only; validates the sizes and stores the scratch bytes in *scratch_bytes (may be NULL).
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_RENDER_MAX_SIDE 1024
+int m324_render_plan(int n_vertices, int n_faces, int frames, int size, long* scratch_bytes);
+int m324_render_project(const float* vertices, long stride_t, int n_vertices, int n_faces, int frames, const float* view, int size,
+                        void* scratch, long scratch_bytes, void* stream);
+int m324_render_raster(const int* faces, int n_faces, int n_vertices, int frames, int size, int big_pixels, void* scratch,
+                       long scratch_bytes, void* stream);
+int m324_render_shade(const int* faces, int n_faces, int n_vertices, int frames, int size, const float* colors, const float* normals,
+                      long normal_stride_t, const float* view, float ambient, int background, unsigned char* rgb, int* face, int* depth,
+                      void* scratch, long scratch_bytes, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

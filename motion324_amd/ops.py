@@ -882,6 +882,13 @@ def _device_array(t, dtype: torch.dtype, name: str) -> torch.Tensor:
     return t.detach().contiguous()
 
 
+def _faces_in_range(f: torch.Tensor, n_vertices: int, name: str) -> None:
+    """the host-side range check of a face list in front of kernels that do not check it: one device reduction and a sync"""
+    lo, hi = (int(x) for x in torch.aminmax(f))
+    if lo < 0 or hi >= n_vertices:
+        raise L.M324Error(f"{name}: faces index vertices {lo}..{hi}, the mesh has {n_vertices}")
+
+
 def _surface_mesh(vertices, faces, name: str, faces_checked: bool):
     """(vertices fp64 contiguous, faces int32 contiguous, batch, stride_v in elements, batched); the kernels do not check
     vertex indices, so the range of `faces` is checked here (one device reduction and a sync) unless the caller did it on the
@@ -895,9 +902,7 @@ def _surface_mesh(vertices, faces, name: str, faces_checked: bool):
     if f.device != v.device:
         raise L.M324Error(f"{name}: vertices and faces live on different devices")
     if not faces_checked:
-        lo, hi = (int(x) for x in torch.aminmax(f))
-        if lo < 0 or hi >= v.shape[-2]:
-            raise L.M324Error(f"{name}: faces index vertices {lo}..{hi}, the mesh has {v.shape[-2]}")
+        _faces_in_range(f, v.shape[-2], name)
     batched = v.dim() == 3
     return v, f, (v.shape[0] if batched else 1), (v.shape[-2] * 3 if batched else 0), batched
 
@@ -1216,6 +1221,134 @@ def frame_resample(src: torch.Tensor, coef: torch.Tensor, bounds: torch.Tensor, 
                                          int(paste[0]), int(paste[1]), int(fill), _stream()), "m324_frame_resample")
     _wrote(out)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ mesh clip rendering
+RENDER_BIG_PIXELS = 64          # default of big_pixels, measured against 16 / 256 / 1024 (profiles/mesh_render.md); never in the result
+
+
+def render_plan(n_vertices: int, n_faces: int, frames: int, size: int) -> int:
+    """scratch bytes of the three render entry points for these sizes: m324_render_plan, host-only"""
+    need = C.c_long(0)
+    L.check(L.load().m324_render_plan(int(n_vertices), int(n_faces), int(frames), int(size), C.addressof(need)), "m324_render_plan")
+    return int(need.value)
+
+
+def _render_view(view, name: str):
+    """the row-major 3 x 4 view matrix as 12 host floats"""
+    import numpy as np
+    m = np.ascontiguousarray(np.asarray(view, dtype=np.float32))
+    if m.shape != (3, 4):
+        raise L.M324Error(f"{name}: the view matrix is 3 x 4, got {m.shape}")
+    return m
+
+
+def _render_clip(vertices, name: str):
+    """fp32 device clip [T,V,3] -> (tensor, stride_t in elements); a view whose last two axes are contiguous is used in place"""
+    if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda:
+        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    if vertices.dtype != torch.float32:
+        raise L.M324Error(f"{name}: expected torch.float32, got {vertices.dtype}")
+    v = vertices.detach()
+    if v.dim() != 3 or v.shape[2] != 3 or 0 in v.shape:
+        raise L.M324Error(f"{name}: expected non-empty fp32 vertices [T,V,3], got {tuple(v.shape)}")
+    if v.stride(2) != 1 or v.stride(1) != 3 or (v.shape[0] > 1 and v.stride(0) < 0):
+        v = v.contiguous()
+    return v, (v.stride(0) if v.shape[0] > 1 else v.shape[1] * 3)
+
+
+def _render_faces(faces, n_vertices: int, device, name: str, faces_checked: bool) -> torch.Tensor:
+    """int32 faces [F,3] on the clip's device; their range is checked here (one reduction and a sync), as _surface_mesh does,
+    unless the caller did it already"""
+    f = _device_array(faces, torch.int32, f"{name}: faces")
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] == 0:
+        raise L.M324Error(f"{name}: expected non-empty [F,3] int32 faces, got {tuple(f.shape)}")
+    if f.device != device:
+        raise L.M324Error(f"{name}: vertices and faces live on different devices")
+    if not faces_checked:
+        _faces_in_range(f, n_vertices, name)
+    return f
+
+
+def _render_scratch(scratch, need: int, device, name: str) -> torch.Tensor:
+    if scratch is None:
+        return torch.empty((need,), dtype=torch.uint8, device=device)
+    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.dtype != torch.uint8 or not scratch.is_contiguous() \
+            or scratch.numel() < need or scratch.device != device:
+        raise L.M324Error(f"{name}: scratch must be a contiguous uint8 device tensor of at least {need} bytes (render_plan)")
+    return scratch
+
+
+def render_project(vertices: torch.Tensor, view, size: int, n_faces: int, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Projects every vertex of a clip (m324_render_project): vertices fp32 [T,V,3] (a view with contiguous last two axes is used
+    in place), view = the 3 x 4 matrix.  Returns the scratch buffer the raster and shade steps continue on."""
+    v, stride_t = _render_clip(vertices, "render_project: vertices")
+    m = _render_view(view, "render_project")
+    T, nv = v.shape[0], v.shape[1]
+    need = render_plan(nv, n_faces, T, size)
+    scratch = _render_scratch(scratch, need, v.device, "render_project")
+    L.check(L.load().m324_render_project(_p(v), stride_t, nv, int(n_faces), T, m.ctypes.data, int(size), _p(scratch), scratch.numel(), _stream()),
+            "m324_render_project")
+    _wrote(scratch)
+    return scratch
+
+
+def render_raster(faces: torch.Tensor, n_vertices: int, frames: int, size: int, scratch: torch.Tensor, big_pixels: Optional[int] = None,
+                  faces_checked: bool = False) -> torch.Tensor:
+    """Fills the (depth, face) keys of every frame (m324_render_raster) on the scratch render_project returned.  big_pixels:
+    boxes larger than this go through the queued pass; None = RENDER_BIG_PIXELS.  The keys do not depend on it."""
+    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda:
+        raise L.M324Error("render_raster: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    f = _render_faces(faces, int(n_vertices), scratch.device, "render_raster", faces_checked)
+    need = render_plan(n_vertices, f.shape[0], frames, size)
+    scratch = _render_scratch(scratch, need, scratch.device, "render_raster")
+    big = RENDER_BIG_PIXELS if big_pixels is None else int(big_pixels)
+    if not 0 <= big <= 2 ** 31 - 1:
+        raise L.M324Error(f"render_raster: big_pixels must be in 0..2^31-1, got {big_pixels}")
+    L.check(L.load().m324_render_raster(_p(f), f.shape[0], int(n_vertices), int(frames), int(size), big, _p(scratch), scratch.numel(), _stream()),
+            "m324_render_raster")
+    _wrote(scratch)
+    return scratch
+
+
+def render_shade(faces: torch.Tensor, n_vertices: int, frames: int, size: int, scratch: torch.Tensor, view, *,
+                 colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, ambient: float = 0.3,
+                 background=(0, 0, 0), out=None, faces_checked: bool = False):
+    """Resolves the keys into (rgb uint8 [T,S,S,3], face int32 [T,S,S], depth int32 [T,S,S]) (m324_render_shade).  colors fp32
+    [V,3]; normals fp32 [T,V,3] (model space) selects smooth shading, None flat; out: the three tensors to write, dense."""
+    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda:
+        raise L.M324Error("render_shade: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    dev = scratch.device
+    T, S, nv = int(frames), int(size), int(n_vertices)
+    f = _render_faces(faces, nv, dev, "render_shade", faces_checked)
+    m = _render_view(view, "render_shade")
+    need = render_plan(nv, f.shape[0], T, S)
+    scratch = _render_scratch(scratch, need, dev, "render_shade")
+    col = None
+    if colors is not None:
+        col = _device_array(colors, torch.float32, "render_shade: colors")
+        if tuple(col.shape) != (nv, 3) or col.device != dev:
+            raise L.M324Error(f"render_shade: colors must be fp32 [{nv},3] on the clip's device, got {tuple(col.shape)}")
+    vn, normal_stride = None, 0
+    if normals is not None:
+        vn, normal_stride = _render_clip(normals, "render_shade: normals")
+        if tuple(vn.shape) != (T, nv, 3) or vn.device != dev:
+            raise L.M324Error(f"render_shade: normals must be fp32 [{T},{nv},3] on the clip's device, got {tuple(vn.shape)}")
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or any(not 0 <= c <= 255 for c in bg) or not 0.0 <= float(ambient) <= 1.0:
+        raise L.M324Error(f"render_shade: background is three bytes and ambient lies in [0, 1], got {background!r}, {ambient!r}")
+    if out is None:
+        out = (torch.empty((T, S, S, 3), dtype=torch.uint8, device=dev), torch.empty((T, S, S), dtype=torch.int32, device=dev),
+               torch.empty((T, S, S), dtype=torch.int32, device=dev))
+    rgb, face, depth = out
+    for t, shape, dt, what in ((rgb, (T, S, S, 3), torch.uint8, "rgb"), (face, (T, S, S), torch.int32, "face"), (depth, (T, S, S), torch.int32, "depth")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise L.M324Error(f"render_shade: out {what} must be a contiguous {dt} device tensor {shape}")
+    L.check(L.load().m324_render_shade(_p(f), f.shape[0], nv, T, S, _p(col), _p(vn), normal_stride, m.ctypes.data, float(ambient),
+                                       bg[0] | bg[1] << 8 | bg[2] << 16, _p(rgb), _p(face), _p(depth), _p(scratch), scratch.numel(), _stream()),
+            "m324_render_shade")
+    _wrote(rgb, face, depth)
+    return rgb, face, depth
 
 
 # ------------------------------------------------------------------------------------------------ training side
