@@ -189,8 +189,8 @@ class DinoEncoder(nn.Module):
                 ops.layernorm(x[r], *w["n1"], DINO_EPS, h[r])
                 src, wq, bq, lnk = h[r], w["qkv"][0], w["qkv"][1], {}
             if fused:
-                proj(src, wq, None, bias=bq,
-                     qkv_heads=(Qh[f0:f1], Kh[f0:f1], Vh[f0:f1], None, None, 0.0, ops.Q_PRESCALE, Lt, H), **lnk)
+                proj(src, wq, None, bias=bq, **lnk,
+                     qkv_heads=ops.QKVHeads(Qh[f0:f1], Kh[f0:f1], Vh[f0:f1], q_w=None, k_w=None, eps=0.0, q_scale=ops.Q_PRESCALE, L=Lt, H=H))
                 ops.attention(Qh[f0:f1], Kh[f0:f1], Vh[f0:f1], h[r], prescaled=True, v_rowmajor=True)
             else:
                 proj(src, wq, qkv[r], bias=bq, **lnk)

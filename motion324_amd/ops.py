@@ -35,18 +35,53 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _is_device(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
+def _on_device(t, name: str = "") -> None:
+    """Refuses whatever is not a HIP device tensor; `name` (the wrapper, or "wrapper: operand") leads the message."""
+    if not _is_device(t):
+        raise L.M324Error((name + ": " if name else "") + "libm324 ops need HIP device tensors (no CPU fallback on this path)")
+
+
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     if t is None:
         return None
-    if not t.is_cuda:
-        raise L.M324Error("libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(t)
     return t.data_ptr()
 
 
+def _launch(name: str, *args) -> None:
+    """One stream-ordered libm324 call, enqueued on torch's current stream; a failure is reported under the same `name`."""
+    L.check(getattr(L.load(), name)(*args, _stream()), name)
+
+
+def _plan_query(name: str, *args):
+    """(count, bytes needed) of a host-only m324_*_plan query: the call returns its count (m324_render_plan has none: 0), or a
+    negative status"""
+    need = C.c_long(0)
+    n = int(getattr(L.load(), name)(*args, C.addressof(need)))
+    L.check(0 if n > 0 else n, name)
+    return n, int(need.value)
+
+
+def _row_extent(n: int, gin: int, gout: int, off: int) -> int:
+    """rows a row-mapped operand must have for n mapped rows: row m lives at (m // gin) * gout + m % gin + off (gin > 0)"""
+    return (n - 1) // gin * gout + (n - 1) % gin + off + 1
+
+
 def _wrote(*tensors) -> None:
-    """libm324 writes through raw pointers: torch's in-place version counters do not see it.  Every wrapper marks the tensors
-    its kernels write, so that `_version`-keyed caches (backward.Carry's bf16 twin of a gradient, the Prepared weight stamp) are
-    invalidated by library writes exactly as by torch writes."""
+    """libm324 writes through raw pointers: torch's in-place version counters do not see it.  A mark is REQUIRED wherever a
+    `_version`-keyed cache can see the written tensor.  The caches, and what covers each:
+      backward.Carry (the bf16 twin of a gradient dx): a dx it holds is written only through gemm()'s plain mode and
+        layernorm_bwd, and both mark it;
+      Prepared's stamps and mirrors (parameters): only the optimizer wrappers (adamw_step, adamw_flat, weight_mirror) write
+        them, and those do NOT mark -- optim calls prepared.bump_generation() after its raw writes, which the stamps include;
+      _CORNER_CACHE (vertex_corners) and dataset's topology cache (a faces tensor): no kernel writes faces; the geometry,
+        surface, framing and render wrappers mark the outputs they return, so a tensor made by one of them is covered.
+    Everywhere else a mark is a courtesy, and the set is incomplete: layernorm, attention, rowstats*, cast, colsum(out=),
+    gemm(n3=) and the direct gemm_tn(out=) path, among others, write without one.  tests/test_ops_calls_cpu.py pins the set."""
     for t in tensors:
         if t is not None:
             torch.autograd.graph.increment_version(t)
@@ -122,7 +157,7 @@ def gemm_splitk(a: torch.Tensor, w: torch.Tensor, slices: int) -> torch.Tensor:
     args.batch, args.strideA, args.strideW, args.strideC = slices, ks, ks, M * N
     with span(f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * main, esz * (M + N) * main + 4.0 * slices * M * N,
               f"split-K M={M} N={N} K={main} slices={slices}" if _timing() else ""):
-        L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
+        _launch("m324_gemm", C.byref(args))
     if main < K:                                        # remainder of the contraction
         gemm(a[:, main:], w[:, main:], part[slices])
     return colsum(part.reshape(part.shape[0], M * N)).reshape(M, N)
@@ -155,7 +190,7 @@ def gemm_tn(x: torch.Tensor, y: torch.Tensor, slices: int = 1, out: Optional[tor
     py, ldy = _rows(y, "y")
     with span("gemm_bf16", 2.0 * M * N * Kc, 2.0 * M * (N + Kc) + 4.0 * slices * N * Kc,
               f"TN M={N} N={Kc} K={M} slices={slices}" if _timing() else ""):
-        L.check(L.load().m324_gemm_tn(px, ldx, py, ldy, _p(part), Kc, M, N, Kc, slices, N * Kc, _stream()), "m324_gemm_tn")
+        _launch("m324_gemm_tn", px, ldx, py, ldy, _p(part), Kc, M, N, Kc, slices, N * Kc)
     if slices == 1 and not accumulate:
         return out if direct else part[0]
     if out is not None:
@@ -170,45 +205,50 @@ def gemm_tn(x: torch.Tensor, y: torch.Tensor, slices: int = 1, out: Optional[tor
     return colsum(part.reshape(slices, N * Kc)).reshape(N, Kc)
 
 
-def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act: int = L.ACT_NONE, gamma=None,
-         residual: Optional[torch.Tensor] = None, res_rows: int = 0, row_map=(0, 0, 0),
-         preact_out: Optional[torch.Tensor] = None, gelu_grad_of: Optional[torch.Tensor] = None,
-         gelu_grad_out: Optional[torch.Tensor] = None, mul_by: Optional[torch.Tensor] = None,
-         qkv_heads: Optional[tuple] = None, n3: Optional[tuple] = None, ln: Optional[tuple] = None,
-         stats_out: Optional[torch.Tensor] = None, copy_out: Optional[torch.Tensor] = None, defer: Optional[list] = None,
-         in_rows: Optional[tuple] = None) -> torch.Tensor:
-    """out[row_map(m), :N] = epilogue(a[M,K] @ w[N,K]^T); see include/m324.h m324_gemm.
-    in_rows = (gin, gout, off) (m324_gemm_rows): M = out.shape[0], and row m reads row (m // gin) * gout + m % gin + off of `a` and
-    of `residual`; out, stats_out and copy_out are compact.  Built for the fp32 LayerNorm-statistics producer only.
-    preact_out [M, N] (out's dtype) also receives the value the activation is applied to (M324_AUX_STORE_PREACT);
-    gelu_grad_of [M, N] = z: the result is multiplied by gelu'(z) (M324_AUX_MUL_GELU_GRAD).  Training only.
-    gelu_grad_out [M, N] receives gelu'(pre-activation) (M324_AUX_STORE_GELU_GRAD) and mul_by [M, N] multiplies the result
-    (M324_AUX_MUL): the same pair with erf evaluated once, in the forward.
-    qkv_heads = (Q, K, V, q_w, k_w, eps, q_scale, L, H): the fused q|k|v projection is written head-major into Q / K / V
-    [B, H, L, 64] with per-head RMSNorm and the q pre-scale (M324_AUX_QKV_HEADS); `out` is ignored (may be None).
-    A V of shape [B, H, 64, L] selects M324_AUX_QKV_HEADS_VT: V leaves transposed and key-permuted, the operand
-    attention() reads by default (L % 128 == 0).
-    defer (qkv_heads only): a list that receives the prepared call instead of a launch; gemm_pair(list) then runs two of them
-    as ONE launch (m324_gemm_pair).
-    LayerNorm fold (include/m324.h): ln = (rowstat fp32 [M, 2], colsum fp32 [N]) -- `a` is the raw stream, `w` carries the
-    LayerNorm scale; ln = (part fp32 [K / 64, M, 2], colsum, eps): the producer's stats_out itself, merged by this GEMM; stats_out fp32 [N / 64, M, 2] receives the per-block row statistics of the stored values and copy_out
-    bf16 [M, N] their bf16 twin (fp32 `out` only)."""
-    M, K = a.shape
-    N = w.shape[0]
-    if w.shape[1] != K or a.dtype != w.dtype:
-        raise L.M324Error(f"gemm: a{tuple(a.shape)} {a.dtype} vs w{tuple(w.shape)} {w.dtype}")
-    if in_rows is not None:
-        gin_i, gout_i, off_i = (int(v) for v in in_rows)
-        M = out.shape[0] if out is not None else 0
-        src_need = ((M - 1) // gin_i * gout_i + (M - 1) % gin_i + off_i + 1) if gin_i > 0 and M > 0 else 0
-        if (gin_i <= 0 or M <= 0 or qkv_heads is not None or n3 is not None or residual is None or a.shape[0] < src_need
-                or residual.shape[0] < src_need or residual.data_ptr() == out.data_ptr()):
-            raise L.M324Error(f"gemm: in_rows {tuple(in_rows)} needs an output of M rows, a and a residual (not the output) of "
-                              f"{src_need} rows: a{tuple(a.shape)}")
-    args = L.GemmArgs()
-    args.A, args.lda = _rows(a, "a")
-    args.W, args.ldw = _rows(w, "w")
-    args.M, args.N, args.K = M, N, K
+class QKVHeads(NamedTuple):
+    """gemm(qkv_heads=...), gemm_mx(qkv_heads=...): the fused q|k|v projection is written head-major into Q / K / V
+    [B, H, L, 64] with per-head RMSNorm (q_w, k_w: fp32 [64] or None; eps) and the q pre-scale q_scale (M324_AUX_QKV_HEADS);
+    the GEMM's `out` is ignored (may be None).  Q None = the k|v projection of a cross-attention, K and V None = its q
+    projection.  A V of shape [B, H, 64, L] selects M324_AUX_QKV_HEADS_VT: V leaves transposed and key-permuted, the operand
+    attention() reads by default (L % 128 == 0).  vt asks for that form outright; None = V has the transposed shape and L != 64.
+    A plain tuple of the first nine or of all ten entries is taken wherever a QKVHeads is."""
+    Q: Optional[torch.Tensor]
+    K: Optional[torch.Tensor]
+    V: Optional[torch.Tensor]
+    q_w: Optional[torch.Tensor]
+    k_w: Optional[torch.Tensor]
+    eps: float
+    q_scale: float
+    L: int
+    H: int
+    vt: Optional[bool] = None
+
+
+def _qkv_heads_args(args, heads, M: int, N: int, who: str) -> torch.Tensor:
+    """Validates `heads` (QKVHeads) for a projection of M rows and N columns and fills its part of `args`: C / ldc, the output
+    dtype, aux_mode and the qkv_* fields.  Marks the outputs as written and returns the first one given."""
+    h = QKVHeads(*heads)
+    Bh = M // h.L
+    vt = h.vt if h.vt is not None else (h.V is not None and tuple(h.V.shape) == (Bh, h.H, 64, h.L) and h.L != 64)
+    outs = [t for t in (h.Q, h.K, h.V) if t is not None]
+    for t in outs:
+        want = (Bh, h.H, 64, h.L) if (vt and t is h.V) else (Bh, h.H, h.L, 64)
+        if t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != want:
+            raise L.M324Error(f"{who}: qkv_heads output {t.dtype}{tuple(t.shape)} (want bf16 {want})")
+    if vt and h.L % 64:
+        raise L.M324Error(f"{who}: a transposed V output needs L % 64 == 0 (L={h.L})")
+    args.C, args.ldc, args.out_dtype = None, N, BF16
+    args.aux_mode = 4 if vt else 3
+    args.qkv_q, args.qkv_k, args.qkv_v = _p(h.Q), _p(h.K), _p(h.V)
+    args.qkv_qw, args.qkv_kw = _vec(h.q_w, 64, "q_w"), _vec(h.k_w, 64, "k_w")
+    args.qkv_eps, args.qkv_qscale, args.qkv_L, args.qkv_H = h.eps, h.q_scale, h.L, h.H
+    _wrote(*outs)
+    return outs[0]
+
+
+def _gemm_ln_fold(args, a, M: int, N: int, K: int, ln, stats_out, copy_out) -> None:
+    """the LayerNorm-fold arguments of gemm(): the consumer's ln (merged 2-tuple or unmerged 3-tuple), the producer's stats_out
+    and copy_out"""
     if ln is not None and len(ln) == 3:
         part, colsum, eps = ln                       # the producer's unmerged table: the consumer merges its rows' blocks itself
         if (part.dtype != torch.float32 or not part.is_contiguous() or K % 64 or tuple(part.shape) != (K // 64, M, 2) or a.dtype != torch.bfloat16):
@@ -228,53 +268,40 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
         if copy_out.dtype != torch.bfloat16 or copy_out.shape[0] < M or copy_out.shape[1] < N:
             raise L.M324Error(f"gemm: copy_out {copy_out.dtype}{tuple(copy_out.shape)} (want bf16 [{M}, {N}])")
         args.ln_copy_out, args.ln_ldcopy = _rows(copy_out, "copy_out")
-    if qkv_heads is not None:
-        # (Q, K, V, q_w, k_w, eps, q_scale, L, H[, vt]): Q None = the k|v projection of a cross-attention, K and V None = its
-        # q projection; vt (default: V has the transposed shape and L != 64) = V leaves transposed + key-permuted
-        Qo, Ko, Vo, qw, kw, eps, q_scale, Lh, Hh = qkv_heads[:9]
-        Bh = M // Lh
-        vt = qkv_heads[9] if len(qkv_heads) > 9 else (Vo is not None and tuple(Vo.shape) == (Bh, Hh, 64, Lh) and Lh != 64)
-        for t in (Qo, Ko, Vo):
-            if t is None:
-                continue
-            want = (Bh, Hh, 64, Lh) if (vt and t is Vo) else (Bh, Hh, Lh, 64)
-            if t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != want:
-                raise L.M324Error(f"gemm: qkv_heads output {t.dtype}{tuple(t.shape)} (want bf16 {want})")
-        if vt and Lh % 64:
-            raise L.M324Error(f"gemm: a transposed V output needs L % 64 == 0 (L={Lh})")
-        args.C, args.ldc = None, N
-        args.in_dtype, args.out_dtype = code_of(a.dtype), BF16
-        args.bias = _vec(bias, N, "bias")
-        args.aux_mode = 4 if vt else 3
-        args.qkv_q, args.qkv_k, args.qkv_v = _p(Qo), _p(Ko), _p(Vo)
-        args.qkv_qw, args.qkv_kw = _vec(qw, 64, "q_w"), _vec(kw, 64, "k_w")
-        first = next(t for t in (Qo, Ko, Vo) if t is not None)
-        args.qkv_eps, args.qkv_qscale, args.qkv_L, args.qkv_H = eps, q_scale, Lh, Hh
-        if defer is not None:                       # gemm_pair() launches it together with another one
-            defer.append((args, 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N), f"M={M} N={N} K={K} qkv-heads", (a, w, bias, Qo, Ko, Vo, qw, kw)))
-            return first
-        with span("gemm_bf16", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N),
-                  f"{_gemm_plan(args)} | M={M} N={N} K={K} qkv-heads" if _timing() else ""):
-            L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
-        return first
-    if n3 is not None:
-        # n3 = (w3 fp32 [3, N], part fp32 [N / 64, M, 3]): gelu(a w^T + bias) is contracted with w3 in the epilogue
-        # (M324_AUX_N3); `out` is ignored (may be None); finish with n3_finish(part, bias3, out3)
-        w3, part = n3
-        if (a.dtype != torch.bfloat16 or w3.dtype != torch.float32 or tuple(w3.shape) != (3, N) or not w3.is_contiguous()
-                or part.dtype != torch.float32 or tuple(part.shape) != (N // 64, M, 3) or not part.is_contiguous()
-                or residual is not None or gamma is not None or act != L.ACT_GELU or N % 256):
-            raise L.M324Error(f"gemm: n3 mode needs bf16 operands, act=GELU, N % 256 == 0, w3 [3,{N}] and part [{N // 64},{M},3] fp32")
-        args.C, args.ldc = None, N
-        args.in_dtype, args.out_dtype = BF16, BF16
-        args.bias = _vec(bias, N, "bias")
-        args.act = act
-        args.aux, args.ldaux, args.aux_mode = _p(part), 3, 5
-        args.qkv_qw = _p(w3)
-        with span("gemm_bf16", 2.0 * M * N * K + 2.0 * M * N * 3, 2.0 * (M * K + N * K) + 4.0 * part.numel(),
-                  f"{_gemm_plan(args)} | M={M} N={N} K={K} gelu n3" if _timing() else ""):
-            L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
-        return part
+
+
+# The three modes of gemm(): each fills the rest of `args` for a[M, K] @ w[N, K]^T and returns (what gemm() returns, span class,
+# FLOPs, bytes, the words of the span's tag after the plan -- built only where `tagged`).
+def _gemm_heads(args, a, bias, heads, tagged: bool):
+    M, N, K = args.M, args.N, args.K
+    first = _qkv_heads_args(args, heads, M, N, "gemm")
+    args.in_dtype = code_of(a.dtype)
+    args.bias = _vec(bias, N, "bias")
+    return first, "gemm_bf16", 2.0 * M * N * K, 2.0 * (M * K + N * K + M * N), f"M={M} N={N} K={K} qkv-heads" if tagged else ""
+
+
+def _gemm_n3(args, a, bias, act, gamma, residual, n3, tagged: bool):
+    """n3 = (w3 fp32 [3, N], part fp32 [N / 64, M, 3]): gelu(a w^T + bias) is contracted with w3 in the epilogue (M324_AUX_N3);
+    `out` is ignored (may be None); finish with n3_finish(part, bias3, out3)"""
+    M, N, K = args.M, args.N, args.K
+    w3, part = n3
+    if (a.dtype != torch.bfloat16 or w3.dtype != torch.float32 or tuple(w3.shape) != (3, N) or not w3.is_contiguous()
+            or part.dtype != torch.float32 or tuple(part.shape) != (N // 64, M, 3) or not part.is_contiguous()
+            or residual is not None or gamma is not None or act != L.ACT_GELU or N % 256):
+        raise L.M324Error(f"gemm: n3 mode needs bf16 operands, act=GELU, N % 256 == 0, w3 [3,{N}] and part [{N // 64},{M},3] fp32")
+    args.C, args.ldc = None, N
+    args.in_dtype, args.out_dtype = BF16, BF16
+    args.bias = _vec(bias, N, "bias")
+    args.act = act
+    args.aux, args.ldaux, args.aux_mode = _p(part), 3, 5
+    args.qkv_qw = _p(w3)
+    return (part, "gemm_bf16", 2.0 * M * N * K + 2.0 * M * N * 3, 2.0 * (M * K + N * K) + 4.0 * part.numel(),
+            f"M={M} N={N} K={K} gelu n3" if tagged else "")
+
+
+def _gemm_plain(args, a, out, bias, act, gamma, residual, res_rows, row_map, auxes, tagged: bool):
+    """auxes: (preact_out, gelu_grad_of, gelu_grad_out, mul_by), at most one of them given"""
+    M, N, K = args.M, args.N, args.K
     args.C, args.ldc = _rows(out, "out")
     _wrote(out)
     args.in_dtype, args.out_dtype = code_of(a.dtype), code_of(out.dtype)
@@ -288,11 +315,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
         args.residual, args.ldr = _rows(residual, "residual")
         args.res_rows = res_rows
     gin, gout, off = row_map
-    need = ((M - 1) // gin * gout + (M - 1) % gin + off + 1) if gin > 0 else M
+    need = _row_extent(M, gin, gout, off) if gin > 0 else M
     if out.shape[0] < need or out.shape[1] < N:
         raise L.M324Error(f"gemm: out{tuple(out.shape)} too small for {need} x {N}")
     args.row_gin, args.row_gout, args.row_off = gin, gout, off
-    auxes = [(t, mode) for t, mode in ((preact_out, 1), (gelu_grad_of, 2), (gelu_grad_out, 6), (mul_by, 7)) if t is not None]
+    auxes = [(t, mode) for t, mode in zip(auxes, (1, 2, 6, 7)) if t is not None]        # M324_AUX_* of the four
     if auxes:
         if len(auxes) > 1:
             raise L.M324Error("gemm: preact_out, gelu_grad_of, gelu_grad_out and mul_by are mutually exclusive")
@@ -302,22 +329,75 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act:
         args.aux, args.ldaux = _rows(aux, "aux")
         args.aux_mode = mode
     esz = a.element_size()
-    tag = "" if not _timing() else (
-        f"{_gemm_plan(args)} | M={M} N={N} K={K}{' bias' if bias is not None else ''}{' gelu' if act else ''}"
-        f"{' gamma' if gamma is not None else ''}{' res' if residual is not None else ''} out={'bf16' if out.element_size() == 2 else 'f32'}"
-        f"{' ln-fold' if ln is not None else ''}{' ln-stats' if stats_out is not None else ''}")
     # algorithmic bytes: both operands once, the output once, the fp32 residual rows once
     nbytes = esz * (M * K + N * K) + out.element_size() * M * N
     if residual is not None:
         nbytes += residual.element_size() * N * (res_rows if 0 < res_rows < M else M)
-    if copy_out is not None:
-        nbytes += 2 * M * N
-    with span(f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * K, nbytes, tag + (f" in_rows={tuple(in_rows)}" if tag and in_rows else "")):
+    what = "" if not tagged else (
+        f"M={M} N={N} K={K}{' bias' if bias is not None else ''}{' gelu' if act else ''}"
+        f"{' gamma' if gamma is not None else ''}{' res' if residual is not None else ''} out={'bf16' if out.element_size() == 2 else 'f32'}")
+    return out, f"gemm_{'bf16' if esz == 2 else 'f32'}", 2.0 * M * N * K, nbytes, what
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, act: int = L.ACT_NONE, gamma=None,
+         residual: Optional[torch.Tensor] = None, res_rows: int = 0, row_map=(0, 0, 0),
+         preact_out: Optional[torch.Tensor] = None, gelu_grad_of: Optional[torch.Tensor] = None,
+         gelu_grad_out: Optional[torch.Tensor] = None, mul_by: Optional[torch.Tensor] = None,
+         qkv_heads: Optional[tuple] = None, n3: Optional[tuple] = None, ln: Optional[tuple] = None,
+         stats_out: Optional[torch.Tensor] = None, copy_out: Optional[torch.Tensor] = None, defer: Optional[list] = None,
+         in_rows: Optional[tuple] = None) -> torch.Tensor:
+    """out[row_map(m), :N] = epilogue(a[M,K] @ w[N,K]^T); see include/m324.h m324_gemm.
+    in_rows = (gin, gout, off) (m324_gemm_rows): M = out.shape[0], and row m reads row (m // gin) * gout + m % gin + off of `a` and
+    of `residual`; out, stats_out and copy_out are compact.  Built for the fp32 LayerNorm-statistics producer only.
+    preact_out [M, N] (out's dtype) also receives the value the activation is applied to (M324_AUX_STORE_PREACT);
+    gelu_grad_of [M, N] = z: the result is multiplied by gelu'(z) (M324_AUX_MUL_GELU_GRAD).  Training only.
+    gelu_grad_out [M, N] receives gelu'(pre-activation) (M324_AUX_STORE_GELU_GRAD) and mul_by [M, N] multiplies the result
+    (M324_AUX_MUL): the same pair with erf evaluated once, in the forward.
+    qkv_heads: a QKVHeads -- the head-major q|k|v outputs replace `out`; n3: see _gemm_n3.
+    defer (qkv_heads only): a list that receives the prepared call instead of a launch; gemm_pair(list) then runs two of them
+    as ONE launch (m324_gemm_pair).
+    LayerNorm fold (include/m324.h): ln = (rowstat fp32 [M, 2], colsum fp32 [N]) -- `a` is the raw stream, `w` carries the
+    LayerNorm scale; ln = (part fp32 [K / 64, M, 2], colsum, eps): the producer's stats_out itself, merged by this GEMM; stats_out fp32 [N / 64, M, 2] receives the per-block row statistics of the stored values and copy_out
+    bf16 [M, N] their bf16 twin (fp32 `out` only)."""
+    M, K = a.shape
+    N = w.shape[0]
+    if w.shape[1] != K or a.dtype != w.dtype:
+        raise L.M324Error(f"gemm: a{tuple(a.shape)} {a.dtype} vs w{tuple(w.shape)} {w.dtype}")
+    if in_rows is not None:
+        gin, gout, off = rows = tuple(int(v) for v in in_rows)
+        M = out.shape[0] if out is not None else 0
+        src_need = _row_extent(M, gin, gout, off) if gin > 0 and M > 0 else 0
+        if (gin <= 0 or M <= 0 or qkv_heads is not None or n3 is not None or residual is None or a.shape[0] < src_need
+                or residual.shape[0] < src_need or residual.data_ptr() == out.data_ptr()):
+            raise L.M324Error(f"gemm: in_rows {tuple(in_rows)} needs an output of M rows, a and a residual (not the output) of "
+                              f"{src_need} rows: a{tuple(a.shape)}")
+    args = L.GemmArgs()
+    args.A, args.lda = _rows(a, "a")
+    args.W, args.ldw = _rows(w, "w")
+    args.M, args.N, args.K = M, N, K
+    _gemm_ln_fold(args, a, M, N, K, ln, stats_out, copy_out)
+    tagged = _timing() or defer is not None
+    if qkv_heads is not None:
+        ret, cls, flops, nbytes, what = _gemm_heads(args, a, bias, qkv_heads, tagged)
+        if defer is not None:                       # gemm_pair() launches it together with another one
+            defer.append((args, flops, nbytes, what, (a, w, bias) + tuple(qkv_heads[:5])))        # ... and Q, K, V, q_w, k_w stay alive
+            return ret
+    elif n3 is not None:
+        ret, cls, flops, nbytes, what = _gemm_n3(args, a, bias, act, gamma, residual, n3, tagged)
+    else:
+        ret, cls, flops, nbytes, what = _gemm_plain(args, a, out, bias, act, gamma, residual, res_rows, row_map,
+                                                    (preact_out, gelu_grad_of, gelu_grad_out, mul_by), tagged)
+        if copy_out is not None:
+            nbytes += 2 * M * N
+        if what:
+            what += (f"{' ln-fold' if ln is not None else ''}{' ln-stats' if stats_out is not None else ''}"
+                     f"{f' in_rows={tuple(in_rows)}' if in_rows else ''}")
+    with span(cls, flops, nbytes, f"{_gemm_plan(args)} | {what}" if _timing() else ""):
         if in_rows is not None:
-            L.check(L.load().m324_gemm_rows(C.byref(args), gin_i, gout_i, off_i, _stream()), "m324_gemm_rows")
+            _launch("m324_gemm_rows", C.byref(args), *rows)
         else:
-            L.check(L.load().m324_gemm(C.byref(args), _stream()), "m324_gemm")
-    return out
+            _launch("m324_gemm", C.byref(args))
+    return ret
 
 
 class MX(NamedTuple):
@@ -352,7 +432,7 @@ def mx_quant(x: torch.Tensor, out: Optional[MX] = None) -> MX:
     px, ldx = _rows(x, "x")
     pq, lq, ps, ls = _mx_rows(out, rows, K, "out")
     with span("hbm_pass", 0.0, float(rows) * K * (x.element_size() + 1), f"mx_quant_kernel | rows={rows} K={K}" if _timing() else ""):
-        L.check(L.load().m324_mx_quant(px, code_of(x.dtype), ldx, rows, K, pq, lq, ps, ls, _stream()), "m324_mx_quant")
+        _launch("m324_mx_quant", px, code_of(x.dtype), ldx, rows, K, pq, lq, ps, ls)
     _wrote(out.q, out.s)
     return out
 
@@ -366,15 +446,14 @@ def layernorm_mx(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], ep
     px, ldx = _rows(x, "x")
     pq, lq, ps, ls = _mx_rows(out, rows, Cdim, "out")
     with span("hbm_pass", 0.0, float(rows) * Cdim * 5, f"layernorm_mx_kernel | rows={rows} C={Cdim}" if _timing() else ""):
-        L.check(L.load().m324_layernorm_mx(px, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, rows, Cdim, pq, lq, ps, ls, _stream()),
-                "m324_layernorm_mx")
+        _launch("m324_layernorm_mx", px, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, rows, Cdim, pq, lq, ps, ls)
     _wrote(out.q, out.s)
     return out
 
 
 def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, residual: Optional[torch.Tensor] = None,
             qkv_heads: Optional[tuple] = None):
-    """out = epilogue(a @ w^T) on MX operands (m324_gemm_mx).  Epilogues: `out` bf16 [M, N] (+ bias); qkv_heads as in gemm()
+    """out = epilogue(a @ w^T) on MX operands (m324_gemm_mx).  Epilogues: `out` bf16 [M, N] (+ bias); qkv_heads, a QKVHeads
     (`out` None); `out` the fp32 residual stream with residual=out (+ bias, * gamma); `out` an MX operand [M, N] (+ bias, GELU
     with act=ACT_GELU).  Returns `out` (the first head-major output for qkv_heads)."""
     M, K = a.q.shape[0], a.q.shape[1]
@@ -391,22 +470,7 @@ def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, 
     pcs, lcs = None, 0
     first = out
     if qkv_heads is not None:
-        Qo, Ko, Vo, qw, kw, eps, q_scale, Lh, Hh = qkv_heads[:9]
-        Bh = M // Lh
-        vt = Vo is not None and tuple(Vo.shape) == (Bh, Hh, 64, Lh) and Lh != 64
-        for t in (Qo, Ko, Vo):
-            if t is None:
-                continue
-            want = (Bh, Hh, 64, Lh) if (vt and t is Vo) else (Bh, Hh, Lh, 64)
-            if t.dtype != torch.bfloat16 or not t.is_contiguous() or tuple(t.shape) != want:
-                raise L.M324Error(f"gemm_mx: qkv_heads output {t.dtype}{tuple(t.shape)} (want bf16 {want})")
-        args.C, args.ldc, args.out_dtype = None, N, BF16
-        args.aux_mode = 4 if vt else 3
-        args.qkv_q, args.qkv_k, args.qkv_v = _p(Qo), _p(Ko), _p(Vo)
-        args.qkv_qw, args.qkv_kw = _vec(qw, 64, "q_w"), _vec(kw, 64, "k_w")
-        args.qkv_eps, args.qkv_qscale, args.qkv_L, args.qkv_H = eps, q_scale, Lh, Hh
-        first = next(t for t in (Qo, Ko, Vo) if t is not None)
-        _wrote(Qo, Ko, Vo)
+        first = _qkv_heads_args(args, qkv_heads, M, N, "gemm_mx")
     elif isinstance(out, MX):
         args.C, args.ldc, pcs, lcs = _mx_rows(out, M, N, "out")
         args.out_dtype = MXFP8
@@ -421,7 +485,7 @@ def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, 
         _wrote(out)
     with span("gemm_mx", 2.0 * M * N * K, float(M * K + N * K + M * N * 2),
               f"gemm_mx_kernel | M={M} N={N} K={K}" if _timing() else ""):
-        L.check(L.load().m324_gemm_mx(C.byref(args), psa, lsa, psw, lsw, pcs, lcs, _stream()), "m324_gemm_mx")
+        _launch("m324_gemm_mx", C.byref(args), psa, lsa, psw, lsw, pcs, lcs)
     return first
 
 
@@ -431,15 +495,14 @@ def gemm_pair(deferred: list) -> None:
     if len(deferred) != 2:
         raise L.M324Error("gemm_pair: exactly two deferred projections")
     (a0, f0, b0, t0, _), (a1, f1, b1, t1, _) = deferred
-    lib = L.load()
     with span("gemm_bf16", f0 + f1, b0 + b1, f"gemm_ring2_pair_kernel<unsigned short, 4, 0> | {t0} + {t1}" if _timing() else "") as sp:
-        rc = lib.m324_gemm_pair(C.byref(a0), C.byref(a1), _stream())
+        rc = L.load().m324_gemm_pair(C.byref(a0), C.byref(a1), _stream())      # not _launch: "unsupported" is an answer here
         if rc == L.ERR_UNSUPPORTED:
             sp.cancel()                          # nothing ran: the two fallback launches below carry the work
     if rc == L.ERR_UNSUPPORTED:
         for args, fl, by, tag, _ in deferred:
             with span("gemm_bf16", fl, by, f"{_gemm_plan(args)} | {tag}" if _timing() else ""):
-                L.check(lib.m324_gemm(C.byref(args), _stream()), "m324_gemm")
+                _launch("m324_gemm", C.byref(args))
     else:
         L.check(rc, "m324_gemm_pair")
     deferred.clear()
@@ -454,15 +517,14 @@ def layernorm_pair(x0, w0, b0, eps0, out0, x1, w1, b1, eps1, out1, row_map1=(0, 
         raise L.M324Error("layernorm_pair: two fp32 inputs of one width, outputs of one dtype")
     gin, gout, off = row_map1
     rows1 = out1.shape[0]
-    need = ((rows1 - 1) // gin * gout + (rows1 - 1) % gin + off + 1) if gin > 0 else rows1
+    need = _row_extent(rows1, gin, gout, off) if gin > 0 else rows1
     if x1.shape[0] < need:
         raise L.M324Error("layernorm_pair: shape mismatch")
     (p0, l0), (q0, m0), (p1, l1), (q1, m1) = _rows(x0, "x0"), _rows(out0, "out0"), _rows(x1, "x1"), _rows(out1, "out1")
     tag = f"layernorm_pair_kernel | rows={out0.shape[0]}+{rows1} C={Cdim}" if _timing() else ""
     with span("hbm_pass", 0.0, float(out0.shape[0] + rows1) * Cdim * (4 + out0.element_size()), tag):
-        L.check(L.load().m324_layernorm_pair(p0, l0, _vec(w0, Cdim, "w0"), _vec(b0, Cdim, "b0"), eps0, q0, m0, out0.shape[0], 0, 0, 0,
-                                             p1, l1, _vec(w1, Cdim, "w1"), _vec(b1, Cdim, "b1"), eps1, q1, m1, rows1, gin, gout, off,
-                                             Cdim, code_of(out0.dtype), _stream()), "m324_layernorm_pair")
+        _launch("m324_layernorm_pair", p0, l0, _vec(w0, Cdim, "w0"), _vec(b0, Cdim, "b0"), eps0, q0, m0, out0.shape[0], 0, 0, 0,
+                p1, l1, _vec(w1, Cdim, "w1"), _vec(b1, Cdim, "b1"), eps1, q1, m1, rows1, gin, gout, off, Cdim, code_of(out0.dtype))
     _wrote(out0, out1)
 
 
@@ -473,7 +535,7 @@ def rowstats_finish(part: torch.Tensor, eps: float, rowstat: torch.Tensor) -> to
             or not rowstat.is_contiguous() or rowstat.numel() != 2 * M):
         raise L.M324Error("rowstats_finish: part [ncb, M, 2] and rowstat [M, 2] must be contiguous fp32")
     with span("hbm_pass", 0.0, 8.0 * (ncb + 1) * M, f"rowstats_finish_kernel | rows={M} blocks={ncb}" if _timing() else ""):
-        L.check(L.load().m324_rowstats_finish(_p(part), ncb, M, eps, _p(rowstat), _stream()), "m324_rowstats_finish")
+        _launch("m324_rowstats_finish", _p(part), ncb, M, eps, _p(rowstat))
     return rowstat
 
 
@@ -489,7 +551,7 @@ def rowstats(x: torch.Tensor, eps: float, rowstat: torch.Tensor, copy: Optional[
             raise L.M324Error("rowstats: copy must be bf16 [rows, C]")
         pc, ldc = _rows(copy, "copy")
     with span("hbm_pass", 0.0, rows * Cdim * (4.0 + (2.0 if copy is not None else 0.0)), f"rowstats_kernel | rows={rows} C={Cdim}" if _timing() else ""):
-        L.check(L.load().m324_rowstats(px, ldx, rows, Cdim, eps, _p(rowstat), pc, ldc, _stream()), "m324_rowstats")
+        _launch("m324_rowstats", px, ldx, rows, Cdim, eps, _p(rowstat), pc, ldc)
     return rowstat
 
 
@@ -502,18 +564,15 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: 
     Cdim = x.shape[1]
     rows = out.shape[0] if rows is None else rows
     gin, gout, off = row_map
-    need = ((rows - 1) // gin * gout + (rows - 1) % gin + off + 1) if gin > 0 else rows
+    need = _row_extent(rows, gin, gout, off) if gin > 0 else rows
     if x.shape[0] < need or out.shape[0] < rows or out.shape[1] != Cdim:
         raise L.M324Error("layernorm: shape mismatch")
     tag = (f"layernorm_kernel<{'unsigned short' if out.element_size() == 2 else 'float'}, {'unsigned short' if x.element_size() == 2 else 'float'}>"
            f" | rows={rows} C={Cdim}") if _timing() else ""
+    # a bf16 input goes through m324_layernorm_in, which takes the input dtype after the input pointer
+    name, in_dtype = ("m324_layernorm_in", (BF16,)) if x.dtype == torch.bfloat16 else ("m324_layernorm", ())
     with span("hbm_pass", 0.0, float(rows) * Cdim * (x.element_size() + out.element_size()), tag):
-        if x.dtype == torch.bfloat16:
-            L.check(L.load().m324_layernorm_in(px, BF16, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, py, ldy, code_of(out.dtype),
-                                               rows, Cdim, gin, gout, off, _stream()), "m324_layernorm_in")
-        else:
-            L.check(L.load().m324_layernorm(px, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, py, ldy, code_of(out.dtype),
-                                            rows, Cdim, gin, gout, off, _stream()), "m324_layernorm")
+        _launch(name, px, *in_dtype, ldx, _vec(w, Cdim, "w"), _vec(b, Cdim, "b"), eps, py, ldy, code_of(out.dtype), rows, Cdim, gin, gout, off)
     return out
 
 
@@ -552,9 +611,8 @@ def qkv_split(q_src, k_src, v_src, q_w, k_w, eps: float, B: int, Lq: int, H: int
     pq, ldq = src(q_src, "q_src")
     pk, ldk = src(k_src, "k_src")
     pv, ldv = src(v_src, "v_src")
-    L.check(L.load().m324_qkv_split(pq, ldq, pk, ldk, pv, ldv, _vec(q_w, 64, "q_w"), _vec(k_w, 64, "k_w"), eps, q_scale,
-                                    _p(Q), _p(K), _p(V), _p(Qt), _p(Kt), _p(Vt), B, Lq, H, code_of(dtype), _stream()),
-            "m324_qkv_split")
+    _launch("m324_qkv_split", pq, ldq, pk, ldk, pv, ldv, _vec(q_w, 64, "q_w"), _vec(k_w, 64, "k_w"), eps, q_scale,
+            _p(Q), _p(K), _p(V), _p(Qt), _p(Kt), _p(Vt), B, Lq, H, code_of(dtype))
     if train:
         return {"Q": Q, "K": K, "V": V, "Qt": Qt, "Kt": Kt, "Vt": Vt}
     return Q, K, Vt
@@ -586,21 +644,14 @@ def attention(Q: torch.Tensor, K: torch.Tensor, Vt: torch.Tensor, out: torch.Ten
     scale = 64 ** -0.5 if scale is None else scale
     esz = Q.element_size()
     flags = int(prescaled) | (2 if v_rowmajor else 0) | (4 if bounded else 0)       # M324_ATTN_*; the plan query takes shared_q as bit 8
-    if q_rows is not None:
-        nq = min(int(q_rows), Lq)
-        with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * nq * Lk * 64,
-                  esz * 64.0 * H * ((1 if shared_q else B) * nq + 2 * B * Lk + B * nq),
-                  f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk} q_rows={q_rows}"
-                  if _timing() else ""):
-            L.check(L.load().m324_attention_rows(_p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale, flags, _p(lse), code_of(Q.dtype),
-                                                 int(q_rows), _stream()), "m324_attention_rows")
-        return out
-    with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * Lq * Lk * 64,
-              esz * 64.0 * H * ((1 if shared_q else B) * Lq + 2 * B * Lk + B * Lq),
-              f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk}"
+    # q_rows: the other entry point, one more argument, fewer computed queries in the span, a word more in its tag
+    name, nq, rows_arg, rows_tag = ("m324_attention", Lq, (), "") if q_rows is None else \
+        ("m324_attention_rows", min(int(q_rows), Lq), (int(q_rows),), f" q_rows={q_rows}")
+    with span(f"attention_{'bf16' if esz == 2 else 'f32'}", 4.0 * B * H * nq * Lk * 64,
+              esz * 64.0 * H * ((1 if shared_q else B) * nq + 2 * B * Lk + B * nq),
+              f"{_attn_plan(B, H, Lq, Lk, flags | (256 if shared_q else 0), code_of(Q.dtype))} | B={B} H={H} Lq={Lq} Lk={Lk}{rows_tag}"
               if _timing() else ""):
-        L.check(L.load().m324_attention(_p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale, flags, _p(lse), code_of(Q.dtype), _stream()),
-                "m324_attention")
+        _launch(name, _p(Q), qbs, _p(K), _p(Vt), po, ldo, B, H, Lq, Lk, scale, flags, _p(lse), code_of(Q.dtype), *rows_arg)
     return out
 
 
@@ -626,7 +677,7 @@ def attention_merge(parts, out: torch.Tensor, B: int, H: int, Lq: int) -> torch.
     esz = out.element_size()
     with span("hbm_pass", 0.0, float(B * Lq) * H * 64 * esz * (len(parts) + 1),
               f"attention_merge_kernel | rows={B * Lq} parts={len(parts)}" if _timing() else ""):
-        L.check(L.load().m324_attention_merge(*ptrs, ldp, po, ldo, B, H, Lq, code_of(out.dtype), _stream()), "m324_attention_merge")
+        _launch("m324_attention_merge", *ptrs, ldp, po, ldo, B, H, Lq, code_of(out.dtype))
     _wrote(out)
     return out
 
@@ -639,8 +690,7 @@ def patchify(video: torch.Tensor, size: int, patch: int, Kp: int, dtype: torch.d
     Fr, Hin, Win, _ = video.shape
     g = size // patch
     out = torch.empty((Fr * g * g, Kp), dtype=dtype, device=video.device)
-    fn, name = (L.load().m324_patchify_u8, "m324_patchify_u8") if video.dtype == torch.uint8 else (L.load().m324_patchify, "m324_patchify")
-    L.check(fn(_p(video), Fr, Hin, Win, size, patch, _p(out), Kp, code_of(dtype), _stream()), name)
+    _launch("m324_patchify_u8" if video.dtype == torch.uint8 else "m324_patchify", _p(video), Fr, Hin, Win, size, patch, _p(out), Kp, code_of(dtype))
     _wrote(out)
     return out
 
@@ -650,7 +700,7 @@ def point_encode(xyz: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     if xyz.dtype != torch.float32 or not xyz.is_contiguous():
         raise L.M324Error("point_encode: xyz must be contiguous fp32")
     out = torch.empty((xyz.shape[0], 64), dtype=dtype, device=xyz.device)
-    L.check(L.load().m324_point_encode(_p(xyz), xyz.shape[0], _p(out), 64, code_of(dtype), _stream()), "m324_point_encode")
+    _launch("m324_point_encode", _p(xyz), xyz.shape[0], _p(out), 64, code_of(dtype))
     return out
 
 
@@ -662,15 +712,13 @@ def point_concat(normal: torch.Tensor, rgb: torch.Tensor, feat: torch.Tensor, Cd
     P, Kp = feat.shape
     if not feat.is_contiguous() or normal.shape[0] != P or rgb.shape[0] != P:
         raise L.M324Error("point_concat: shape mismatch")
-    L.check(L.load().m324_point_concat(_p(normal), _p(rgb), P, _p(feat), Cdim, Kp, code_of(feat.dtype), _stream()),
-            "m324_point_concat")
+    _launch("m324_point_concat", _p(normal), _p(rgb), P, _p(feat), Cdim, Kp, code_of(feat.dtype))
     return feat
 
 
 def dino_cls_rows(cls: torch.Tensor, pos0: torch.Tensor, x: torch.Tensor, Fr: int, rows_per_frame: int) -> None:
     Cdim = x.shape[1]
-    L.check(L.load().m324_dino_cls_rows(_vec(cls, Cdim, "cls"), _vec(pos0, Cdim, "pos0"), _p(x), Fr, rows_per_frame, Cdim,
-                                        _stream()), "m324_dino_cls_rows")
+    _launch("m324_dino_cls_rows", _vec(cls, Cdim, "cls"), _vec(pos0, Cdim, "pos0"), _p(x), Fr, rows_per_frame, Cdim)
 
 
 def assemble_tokens(dino_x, dino_w, dino_b, eps_dino, pos, sp0, spr, mesh, ln_w, eps_in, B, T, K, P,
@@ -681,10 +729,8 @@ def assemble_tokens(dino_x, dino_w, dino_b, eps_dino, pos, sp0, spr, mesh, ln_w,
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
             raise L.M324Error(f"assemble_tokens: {name} {t.dtype}{tuple(t.shape)} (want {n} fp32)")
     out = torch.empty((B * T * (4 + K + P), Cdim), dtype=torch.float32, device=dino_x.device)
-    L.check(L.load().m324_assemble_tokens(_p(dino_x), _vec(dino_w, Cdim, "dino_w"), _vec(dino_b, Cdim, "dino_b"), eps_dino,
-                                          _p(pos), _p(sp0), _p(spr), _p(mesh), _vec(ln_w, Cdim, "ln_w") if ln_w is not None else None, eps_in, _p(out),
-                                          B, T, K, P, Cdim, float(drop_p), int(drop_seed) & 0xFFFFFFFFFFFFFFFF, _stream()),
-            "m324_assemble_tokens")
+    _launch("m324_assemble_tokens", _p(dino_x), _vec(dino_w, Cdim, "dino_w"), _vec(dino_b, Cdim, "dino_b"), eps_dino, _p(pos), _p(sp0),
+            _p(spr), _p(mesh), _vec(ln_w, Cdim, "ln_w"), eps_in, _p(out), B, T, K, P, Cdim, float(drop_p), int(drop_seed) & 0xFFFFFFFFFFFFFFFF)
     return out
 
 
@@ -695,8 +741,7 @@ def linear_n3(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.T
         raise L.M324Error("linear_n3: w must be contiguous fp32 [3,K]")
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != M * 3:
         raise L.M324Error("linear_n3: out must be contiguous fp32 [M,3]")
-    L.check(L.load().m324_linear_n3(pa, lda, _p(w), _vec(bias, 3, "bias"), _p(out), M, K, code_of(a.dtype), _stream()),
-            "m324_linear_n3")
+    _launch("m324_linear_n3", pa, lda, _p(w), _vec(bias, 3, "bias"), _p(out), M, K, code_of(a.dtype))
     return out
 
 
@@ -706,7 +751,7 @@ def n3_finish(part: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torc
     if three != 3 or part.dtype != torch.float32 or not part.is_contiguous() or out.dtype != torch.float32 \
             or not out.is_contiguous() or out.numel() != M * 3:
         raise L.M324Error("n3_finish: part [ncb, M, 3] and out [M, 3] must be contiguous fp32")
-    L.check(L.load().m324_n3_finish(_p(part), ncb, M, _vec(bias, 3, "bias"), _p(out), _stream()), "m324_n3_finish")
+    _launch("m324_n3_finish", _p(part), ncb, M, _vec(bias, 3, "bias"), _p(out))
     return out
 
 
@@ -717,7 +762,7 @@ def mse(pred: torch.Tensor, target: torch.Tensor, weight: float) -> torch.Tensor
     target = target.contiguous().float()
     partial = torch.empty(1024, dtype=torch.float32, device=pred.device)
     out = torch.empty((), dtype=torch.float32, device=pred.device)
-    L.check(L.load().m324_mse(_p(pred), _p(target), pred.numel(), weight, _p(partial), _p(out), _stream()), "m324_mse")
+    _launch("m324_mse", _p(pred), _p(target), pred.numel(), weight, _p(partial), _p(out))
     return out
 
 
@@ -728,8 +773,7 @@ def smooth_trajectories(trajs: torch.Tensor, threshold: float, sigma: float) -> 
     x = trajs.detach().to(torch.float32).contiguous()
     B, T, N, _ = x.shape
     tmp, out = torch.empty_like(x), torch.empty_like(x)
-    L.check(L.load().m324_smooth_trajectories(_p(x), _p(tmp), _p(out), B, T, N, threshold, sigma, _stream()),
-            "m324_smooth_trajectories")
+    _launch("m324_smooth_trajectories", _p(x), _p(tmp), _p(out), B, T, N, threshold, sigma)
     return out
 
 
@@ -740,7 +784,7 @@ def smooth_savgol(trajs: torch.Tensor, coef: torch.Tensor) -> torch.Tensor:
     if coef.dtype != torch.float64 or not coef.is_cuda or not coef.is_contiguous():
         raise L.M324Error("smooth_savgol: coef must be a contiguous fp64 HIP tensor")
     out = torch.empty_like(x)
-    L.check(L.load().m324_smooth_savgol(_p(x), _p(out), B, T, N, _p(coef), coef.numel(), _stream()), "m324_smooth_savgol")
+    _launch("m324_smooth_savgol", _p(x), _p(out), B, T, N, _p(coef), coef.numel())
     return out
 
 
@@ -748,7 +792,7 @@ def smooth_oneeuro(trajs: torch.Tensor, mincutoff: float, beta: float, dcutoff: 
     x = trajs.detach().to(torch.float32).contiguous()
     B, T, N, _ = x.shape
     out = torch.empty_like(x)
-    L.check(L.load().m324_smooth_oneeuro(_p(x), _p(out), B, T, N, mincutoff, beta, dcutoff, _stream()), "m324_smooth_oneeuro")
+    _launch("m324_smooth_oneeuro", _p(x), _p(out), B, T, N, mincutoff, beta, dcutoff)
     return out
 
 
@@ -759,15 +803,14 @@ def nearest_point(query: torch.Tensor, ref: torch.Tensor) -> torch.Tensor:
     if q.dim() != 2 or q.shape[1] != 3 or r.dim() != 2 or r.shape[1] != 3:
         raise L.M324Error(f"nearest_point: expected [n,3] point sets, got {tuple(q.shape)} / {tuple(r.shape)}")
     idx = torch.empty((q.shape[0],), dtype=torch.int32, device=q.device)
-    L.check(L.load().m324_nearest_point(_p(q), q.shape[0], _p(r), r.shape[0], _p(idx), _stream()), "m324_nearest_point")
+    _launch("m324_nearest_point", _p(q), q.shape[0], _p(r), r.shape[0], _p(idx))
     return idx.long()
 
 
 # ------------------------------------------------------------------------------------------------ geometry evaluation
 def _points(t: torch.Tensor, name: str) -> torch.Tensor:
     """[n,3] or [B,n,3] point set -> contiguous fp32 device tensor (CPU tensors are refused: there is no host path here)"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(t, name)
     if t.dim() not in (2, 3) or t.shape[-1] != 3 or t.shape[-2] == 0 or t.shape[0] == 0:
         raise L.M324Error(f"{name}: expected a non-empty [n,3] or [B,n,3] point set, got {tuple(t.shape)}")
     return t.detach().to(torch.float32).contiguous()
@@ -775,10 +818,7 @@ def _points(t: torch.Tensor, name: str) -> torch.Tensor:
 
 def nn_plan(n_query: int, n_ref: int, batch: int = 1, ref_slices: int = 0):
     """(reference slices, scratch bytes) of the launch m324_nn_search makes for these sizes: m324_nn_plan, host-only"""
-    need = C.c_long(0)
-    slices = int(L.load().m324_nn_plan(n_query, n_ref, batch, ref_slices, C.addressof(need)))
-    L.check(0 if slices > 0 else slices, "m324_nn_plan")
-    return slices, int(need.value)
+    return _plan_query("m324_nn_plan", n_query, n_ref, batch, ref_slices)
 
 
 def nn_search(query: torch.Tensor, ref: torch.Tensor, want_dist: bool = True, want_index: bool = False, ref_slices: int = 0):
@@ -802,8 +842,7 @@ def nn_search(query: torch.Tensor, ref: torch.Tensor, want_dist: bool = True, wa
     shape = (B, nq) if batched else (nq,)
     dist = torch.empty(shape, dtype=torch.float32, device=q.device) if want_dist else None
     index = torch.empty(shape, dtype=torch.int32, device=q.device) if want_index else None
-    L.check(L.load().m324_nn_search(_p(q), stride_q, nq, _p(r), stride_r, nr, B, _p(dist), _p(index), ref_slices, _p(scratch),
-                                    need if slices > 1 else 0, _stream()), "m324_nn_search")
+    _launch("m324_nn_search", _p(q), stride_q, nq, _p(r), stride_r, nr, B, _p(dist), _p(index), ref_slices, _p(scratch), need if slices > 1 else 0)
     _wrote(dist, index)
     if want_dist and want_index:
         return dist, index
@@ -812,8 +851,7 @@ def nn_search(query: torch.Tensor, ref: torch.Tensor, want_dist: bool = True, wa
 
 def dist_stats(dist: torch.Tensor, threshold: float):
     """dist [n] or [B,n] fp32 -> (fp64 sum, int64 count of entries < threshold) per row, deterministic (m324_dist_stats)."""
-    if not isinstance(dist, torch.Tensor) or not dist.is_cuda:
-        raise L.M324Error("dist_stats: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(dist, "dist_stats")
     if dist.dim() not in (1, 2) or dist.numel() == 0 or dist.dtype != torch.float32:
         raise L.M324Error(f"dist_stats: expected a non-empty fp32 [n] or [B,n] tensor, got {dist.dtype}{tuple(dist.shape)}")
     d = dist.detach().contiguous()
@@ -821,14 +859,13 @@ def dist_stats(dist: torch.Tensor, threshold: float):
     partial = torch.empty((B * 64,), dtype=torch.float64, device=d.device)
     total = torch.empty((B,), dtype=torch.float64, device=d.device)
     count = torch.empty((B,), dtype=torch.int64, device=d.device)
-    L.check(L.load().m324_dist_stats(_p(d), n, B, float(threshold), _p(partial), _p(total), _p(count), _stream()), "m324_dist_stats")
+    _launch("m324_dist_stats", _p(d), n, B, float(threshold), _p(partial), _p(total), _p(count))
     _wrote(partial, total, count)
     return (total, count) if dist.dim() == 2 else (total[0], count[0])
 
 
 def _transform_params(params: torch.Tensor, name: str) -> torch.Tensor:
-    if not isinstance(params, torch.Tensor) or not params.is_cuda or params.dtype != torch.float64 or params.numel() != 13 \
-            or not params.is_contiguous():
+    if not _is_device(params) or params.dtype != torch.float64 or params.numel() != 13 or not params.is_contiguous():
         raise L.M324Error(f"{name}: params must be a contiguous fp64 HIP tensor of 13 values (s, R row-major, t)")
     return params
 
@@ -836,14 +873,12 @@ def _transform_params(params: torch.Tensor, name: str) -> torch.Tensor:
 def transform_points(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
     """s * (x @ R.T) + t for fp32 points [..., 3], evaluated in fp64 and rounded once (m324_transform_points); params =
     fp64 device tensor (s, R row-major, t)."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise L.M324Error("transform_points: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(x, "transform_points")
     if x.dim() < 2 or x.shape[-1] != 3 or x.numel() == 0:
         raise L.M324Error(f"transform_points: expected non-empty [..., 3] points, got {tuple(x.shape)}")
     xs = x.detach().to(torch.float32).contiguous()
     out = torch.empty_like(xs)
-    L.check(L.load().m324_transform_points(_p(xs), xs.numel() // 3, _p(_transform_params(params, "transform_points")), _p(out), _stream()),
-            "m324_transform_points")
+    _launch("m324_transform_points", _p(xs), xs.numel() // 3, _p(_transform_params(params, "transform_points")), _p(out))
     _wrote(out)
     return out
 
@@ -854,13 +889,11 @@ def icp_moments(source: torch.Tensor, params: torch.Tensor, target: torch.Tensor
     s, t = _points(source, "icp_moments: source"), _points(target, "icp_moments: target")
     if s.dim() != 2 or t.dim() != 2:
         raise L.M324Error(f"icp_moments: expected [n,3] point sets, got {tuple(s.shape)} / {tuple(t.shape)}")
-    if not isinstance(index, torch.Tensor) or not index.is_cuda or index.dtype != torch.int32 or not index.is_contiguous() \
-            or index.numel() != s.shape[0]:
+    if not _is_device(index) or index.dtype != torch.int32 or not index.is_contiguous() or index.numel() != s.shape[0]:
         raise L.M324Error(f"icp_moments: index must be a contiguous int32 HIP tensor of {s.shape[0]} entries")
     partial = torch.empty((64 * 32,), dtype=torch.float64, device=s.device)
     record = torch.empty((32,), dtype=torch.float64, device=s.device)
-    L.check(L.load().m324_icp_moments(_p(s), s.shape[0], _p(_transform_params(params, "icp_moments")), _p(t), t.shape[0], _p(index),
-                                      _p(partial), _p(record), _stream()), "m324_icp_moments")
+    _launch("m324_icp_moments", _p(s), s.shape[0], _p(_transform_params(params, "icp_moments")), _p(t), t.shape[0], _p(index), _p(partial), _p(record))
     _wrote(partial, record)
     return record
 
@@ -875,8 +908,7 @@ class SurfaceSamples(NamedTuple):
 
 
 def _device_array(t, dtype: torch.dtype, name: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(t, name)
     if t.dtype != dtype:
         raise L.M324Error(f"{name}: expected {dtype}, got {t.dtype}")
     return t.detach().contiguous()
@@ -909,10 +941,7 @@ def _surface_mesh(vertices, faces, name: str, faces_checked: bool):
 
 def surface_plan(n_faces: int, batch: int = 1):
     """(face blocks of the scan, scratch bytes) of m324_surface_cdf for these sizes: m324_surface_plan, host-only"""
-    need = C.c_long(0)
-    blocks = int(L.load().m324_surface_plan(n_faces, batch, C.addressof(need)))
-    L.check(0 if blocks > 0 else blocks, "m324_surface_plan")
-    return blocks, int(need.value)
+    return _plan_query("m324_surface_plan", n_faces, batch)
 
 
 def surface_cdf(vertices: torch.Tensor, faces: torch.Tensor, faces_checked: bool = False) -> torch.Tensor:
@@ -924,7 +953,7 @@ def surface_cdf(vertices: torch.Tensor, faces: torch.Tensor, faces_checked: bool
     _, need = surface_plan(nf, B)
     scratch = torch.empty((need,), dtype=torch.uint8, device=v.device) if need else None
     cdf = torch.empty((B, nf) if batched else (nf,), dtype=torch.float64, device=v.device)
-    L.check(L.load().m324_surface_cdf(_p(v), stride_v, v.shape[-2], _p(f), nf, B, _p(cdf), _p(scratch), need, _stream()), "m324_surface_cdf")
+    _launch("m324_surface_cdf", _p(v), stride_v, v.shape[-2], _p(f), nf, B, _p(cdf), _p(scratch), need)
     _wrote(cdf, scratch)
     return cdf
 
@@ -969,9 +998,8 @@ def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tenso
     face_index = torch.empty(shape, dtype=torch.int32, device=dev) if want_face else None
     normals = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if want_normals else None
     colors = torch.empty(shape + (3,), dtype=torch.float32, device=dev) if want_colors else None
-    L.check(L.load().m324_surface_sample(_p(v), stride_v, nv, _p(f), nf, _p(table), _p(sd), num, B, _p(points), _p(points64), _p(face_index),
-                                         _p(normals), _p(colors), _p(vc), channels, _p(tuv), _p(tex), tex_h, tex_w, _stream()),
-            "m324_surface_sample")
+    _launch("m324_surface_sample", _p(v), stride_v, nv, _p(f), nf, _p(table), _p(sd), num, B, _p(points), _p(points64), _p(face_index),
+            _p(normals), _p(colors), _p(vc), channels, _p(tuv), _p(tex), tex_h, tex_w)
     _wrote(points, points64, face_index, normals, colors)
     return SurfaceSamples(points, points64, face_index, normals, colors)
 
@@ -1048,8 +1076,8 @@ def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, corners: Optiona
     table = _corner_table(corners, faces, f, nv, "vertex_normals")
     frames = v.numel() // (nv * 3)
     out = torch.empty_like(v)
-    L.check(L.load().m324_vertex_normals(_p(v), nv * 3, nv, _p(f), f.shape[0], _p(table.offsets), _p(table.corners), frames,
-                                         NORMAL_WEIGHTINGS[weighting], _p(out), _stream()), "m324_vertex_normals")
+    _launch("m324_vertex_normals", _p(v), nv * 3, nv, _p(f), f.shape[0], _p(table.offsets), _p(table.corners), frames,
+            NORMAL_WEIGHTINGS[weighting], _p(out))
     _wrote(out)
     return out
 
@@ -1114,9 +1142,8 @@ def surface_track(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor
     face_index = torch.empty(lead + (num,), dtype=torch.int32, device=dev) if want_face else None
     normals = torch.empty(lead + (T, num, 3), dtype=torch.float32, device=dev) if vn is not None else None
     colors = torch.empty(lead + (num, 3), dtype=torch.float32, device=dev) if tex is not None else None
-    L.check(L.load().m324_surface_track(_p(v), stride_b, stride_t, nv, _p(f), nf, _p(table), _p(sd), num, B, T, _p(points), _p(points64),
-                                        _p(face_index), _p(vn), stride_b, stride_t, _p(normals), _p(tuv), _p(tex), tex_h, tex_w, _p(colors),
-                                        _stream()), "m324_surface_track")
+    _launch("m324_surface_track", _p(v), stride_b, stride_t, nv, _p(f), nf, _p(table), _p(sd), num, B, T, _p(points), _p(points64),
+            _p(face_index), _p(vn), stride_b, stride_t, _p(normals), _p(tuv), _p(tex), tex_h, tex_w, _p(colors))
     _wrote(points, points64, face_index, normals, colors)
     return TrackedSamples(points, normals, colors, face_index, points64)
 
@@ -1128,17 +1155,13 @@ FRAME_AXES = {"x": 0, "y": 1}
 
 def frame_plan(in_size: int, out_size: int, lines: int = 1, channels: int = 3, frames: int = 1):
     """(ksize, bytes of the pass's result) of one resampling pass: m324_frame_plan, host-only"""
-    need = C.c_long(0)
-    ksize = int(L.load().m324_frame_plan(in_size, out_size, lines, channels, frames, C.addressof(need)))
-    L.check(0 if ksize > 0 else ksize, "m324_frame_plan")
-    return ksize, int(need.value)
+    return _plan_query("m324_frame_plan", in_size, out_size, lines, channels, frames)
 
 
 def _frame_image(t, channels, name: str):
     """uint8 device image stack [T,H,W,>=channels] (or [T,H,W] for one channel) with a unit channel stride -> (pointer, byte
     strides of frame / row / pixel, T, H, W); views with a padded pitch or a wider pixel are taken as they are"""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(t, name)
     if t.dtype != torch.uint8:
         raise L.M324Error(f"{name}: expected uint8, got {t.dtype}")
     if t.dim() == 3 and channels == 1:
@@ -1179,8 +1202,8 @@ def frame_mask(video: torch.Tensor, alpha: Optional[torch.Tensor] = None, *, mod
     masked = torch.empty((T, H, W, 3), dtype=torch.uint8, device=dev) if want_masked else None
     mask = torch.empty((T, H, W), dtype=torch.uint8, device=dev) if want_mask else None
     boxes = torch.empty((T, 4), dtype=torch.int32, device=dev)
-    L.check(L.load().m324_frame_mask(sp, sf, spitch, spix, ap, af, apitch, apix, T, H, W, FRAME_MODES[mode], int(threshold), _p(table),
-                                     _p(masked), _p(mask), _p(boxes), _stream()), "m324_frame_mask")
+    _launch("m324_frame_mask", sp, sf, spitch, spix, ap, af, apitch, apix, T, H, W, FRAME_MODES[mode], int(threshold), _p(table),
+            _p(masked), _p(mask), _p(boxes))
     _wrote(masked, mask, boxes)
     return masked, mask, boxes
 
@@ -1216,9 +1239,9 @@ def frame_resample(src: torch.Tensor, coef: torch.Tensor, bounds: torch.Tensor, 
     dp, df, dpitch, dpix, Td, Hd, Wd = _frame_image(out, channels, "frame_resample: out")
     if Td != T or any(t.device != src.device for t in (coef, bounds, out) + (() if alpha is None else (alpha,))):
         raise L.M324Error("frame_resample: out has another frame count, or the tensors live on different devices")
-    L.check(L.load().m324_frame_resample(sp, sf, spitch, spix, W, H, cx, cy, cw, ch, channels, T, FRAME_AXES[axis], _p(coef), _p(bounds), out_size,
-                                         ksize, ap, af, apitch, apix, FRAME_MODES[mode], int(threshold), _p(table), dp, df, dpitch, dpix, Wd, Hd,
-                                         int(paste[0]), int(paste[1]), int(fill), _stream()), "m324_frame_resample")
+    _launch("m324_frame_resample", sp, sf, spitch, spix, W, H, cx, cy, cw, ch, channels, T, FRAME_AXES[axis], _p(coef), _p(bounds), out_size,
+            ksize, ap, af, apitch, apix, FRAME_MODES[mode], int(threshold), _p(table), dp, df, dpitch, dpix, Wd, Hd,
+            int(paste[0]), int(paste[1]), int(fill))
     _wrote(out)
     return out
 
@@ -1229,9 +1252,7 @@ RENDER_BIG_PIXELS = 64          # default of big_pixels, measured against 16 / 2
 
 def render_plan(n_vertices: int, n_faces: int, frames: int, size: int) -> int:
     """scratch bytes of the three render entry points for these sizes: m324_render_plan, host-only"""
-    need = C.c_long(0)
-    L.check(L.load().m324_render_plan(int(n_vertices), int(n_faces), int(frames), int(size), C.addressof(need)), "m324_render_plan")
-    return int(need.value)
+    return _plan_query("m324_render_plan", int(n_vertices), int(n_faces), int(frames), int(size))[1]
 
 
 def _render_view(view, name: str):
@@ -1245,8 +1266,7 @@ def _render_view(view, name: str):
 
 def _render_clip(vertices, name: str):
     """fp32 device clip [T,V,3] -> (tensor, stride_t in elements); a view whose last two axes are contiguous is used in place"""
-    if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda:
-        raise L.M324Error(f"{name}: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(vertices, name)
     if vertices.dtype != torch.float32:
         raise L.M324Error(f"{name}: expected torch.float32, got {vertices.dtype}")
     v = vertices.detach()
@@ -1273,8 +1293,7 @@ def _render_faces(faces, n_vertices: int, device, name: str, faces_checked: bool
 def _render_scratch(scratch, need: int, device, name: str) -> torch.Tensor:
     if scratch is None:
         return torch.empty((need,), dtype=torch.uint8, device=device)
-    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda or scratch.dtype != torch.uint8 or not scratch.is_contiguous() \
-            or scratch.numel() < need or scratch.device != device:
+    if not _is_device(scratch) or scratch.dtype != torch.uint8 or not scratch.is_contiguous() or scratch.numel() < need or scratch.device != device:
         raise L.M324Error(f"{name}: scratch must be a contiguous uint8 device tensor of at least {need} bytes (render_plan)")
     return scratch
 
@@ -1287,8 +1306,7 @@ def render_project(vertices: torch.Tensor, view, size: int, n_faces: int, scratc
     T, nv = v.shape[0], v.shape[1]
     need = render_plan(nv, n_faces, T, size)
     scratch = _render_scratch(scratch, need, v.device, "render_project")
-    L.check(L.load().m324_render_project(_p(v), stride_t, nv, int(n_faces), T, m.ctypes.data, int(size), _p(scratch), scratch.numel(), _stream()),
-            "m324_render_project")
+    _launch("m324_render_project", _p(v), stride_t, nv, int(n_faces), T, m.ctypes.data, int(size), _p(scratch), scratch.numel())
     _wrote(scratch)
     return scratch
 
@@ -1297,16 +1315,14 @@ def render_raster(faces: torch.Tensor, n_vertices: int, frames: int, size: int, 
                   faces_checked: bool = False) -> torch.Tensor:
     """Fills the (depth, face) keys of every frame (m324_render_raster) on the scratch render_project returned.  big_pixels:
     boxes larger than this go through the queued pass; None = RENDER_BIG_PIXELS.  The keys do not depend on it."""
-    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda:
-        raise L.M324Error("render_raster: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(scratch, "render_raster")
     f = _render_faces(faces, int(n_vertices), scratch.device, "render_raster", faces_checked)
     need = render_plan(n_vertices, f.shape[0], frames, size)
     scratch = _render_scratch(scratch, need, scratch.device, "render_raster")
     big = RENDER_BIG_PIXELS if big_pixels is None else int(big_pixels)
     if not 0 <= big <= 2 ** 31 - 1:
         raise L.M324Error(f"render_raster: big_pixels must be in 0..2^31-1, got {big_pixels}")
-    L.check(L.load().m324_render_raster(_p(f), f.shape[0], int(n_vertices), int(frames), int(size), big, _p(scratch), scratch.numel(), _stream()),
-            "m324_render_raster")
+    _launch("m324_render_raster", _p(f), f.shape[0], int(n_vertices), int(frames), int(size), big, _p(scratch), scratch.numel())
     _wrote(scratch)
     return scratch
 
@@ -1316,8 +1332,7 @@ def render_shade(faces: torch.Tensor, n_vertices: int, frames: int, size: int, s
                  background=(0, 0, 0), out=None, faces_checked: bool = False):
     """Resolves the keys into (rgb uint8 [T,S,S,3], face int32 [T,S,S], depth int32 [T,S,S]) (m324_render_shade).  colors fp32
     [V,3]; normals fp32 [T,V,3] (model space) selects smooth shading, None flat; out: the three tensors to write, dense."""
-    if not isinstance(scratch, torch.Tensor) or not scratch.is_cuda:
-        raise L.M324Error("render_shade: libm324 ops need HIP device tensors (no CPU fallback on this path)")
+    _on_device(scratch, "render_shade")
     dev = scratch.device
     T, S, nv = int(frames), int(size), int(n_vertices)
     f = _render_faces(faces, nv, dev, "render_shade", faces_checked)
@@ -1342,11 +1357,10 @@ def render_shade(faces: torch.Tensor, n_vertices: int, frames: int, size: int, s
                torch.empty((T, S, S), dtype=torch.int32, device=dev))
     rgb, face, depth = out
     for t, shape, dt, what in ((rgb, (T, S, S, 3), torch.uint8, "rgb"), (face, (T, S, S), torch.int32, "face"), (depth, (T, S, S), torch.int32, "depth")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+        if not _is_device(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
             raise L.M324Error(f"render_shade: out {what} must be a contiguous {dt} device tensor {shape}")
-    L.check(L.load().m324_render_shade(_p(f), f.shape[0], nv, T, S, _p(col), _p(vn), normal_stride, m.ctypes.data, float(ambient),
-                                       bg[0] | bg[1] << 8 | bg[2] << 16, _p(rgb), _p(face), _p(depth), _p(scratch), scratch.numel(), _stream()),
-            "m324_render_shade")
+    _launch("m324_render_shade", _p(f), f.shape[0], nv, T, S, _p(col), _p(vn), normal_stride, m.ctypes.data, float(ambient),
+            bg[0] | bg[1] << 8 | bg[2] << 16, _p(rgb), _p(face), _p(depth), _p(scratch), scratch.numel())
     _wrote(rgb, face, depth)
     return rgb, face, depth
 
@@ -1358,7 +1372,7 @@ def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     px, ld = _rows(x, "x")
     rp = (R + 63) // 64 * 64 if rows_pad is None else rows_pad
     out = torch.empty((Cc, rp), dtype=x.dtype, device=x.device)
-    L.check(L.load().m324_transpose(px, ld, _p(out), rp, R, Cc, rp, code_of(x.dtype), _stream()), "m324_transpose")
+    _launch("m324_transpose", px, ld, _p(out), rp, R, Cc, rp, code_of(x.dtype))
     return out
 
 
@@ -1374,8 +1388,7 @@ def colsum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool
     if R >= 256:                                   # two-stage: row chunks in parallel, then a short fixed-order sum
         srows = 256 if R >= 16384 else (64 if R >= 2048 else 16)
         scratch = torch.empty((srows, Cc), dtype=torch.float32, device=x.device)
-    L.check(L.load().m324_colsum(px, ld, _vec(out, Cc, "out"), R, Cc, code_of(x.dtype), int(accumulate), _p(scratch), srows,
-                                 _stream()), "m324_colsum")
+    _launch("m324_colsum", px, ld, _vec(out, Cc, "out"), R, Cc, code_of(x.dtype), int(accumulate), _p(scratch), srows)
     return out
 
 
@@ -1427,7 +1440,7 @@ class _ColsumQueue:
             dsts.append(chain[0][0])
         keep = self.by_dst                                # the sources stay referenced until the launch is enqueued
         self.by_dst, self.count = {}, 0
-        L.check(L.load().m324_colsum_multi(arr, k, _stream()), "m324_colsum_multi")
+        _launch("m324_colsum_multi", arr, k)
         _wrote(*dsts)
         del keep
 
@@ -1450,14 +1463,14 @@ DEFER_COLSUM = switches.flag("M324_DEFER_COLSUM")
 def gelu(z: torch.Tensor) -> torch.Tensor:
     assert z.is_contiguous()
     h = torch.empty_like(z)
-    L.check(L.load().m324_gelu(_p(z), _p(h), z.numel(), code_of(z.dtype), _stream()), "m324_gelu")
+    _launch("m324_gelu", _p(z), _p(h), z.numel(), code_of(z.dtype))
     return h
 
 
 def gelu_bwd(z: torch.Tensor, dh: torch.Tensor) -> torch.Tensor:
     assert z.is_contiguous() and dh.is_contiguous() and z.shape == dh.shape and z.dtype == dh.dtype
     dz = torch.empty_like(z)
-    L.check(L.load().m324_gelu_bwd(_p(z), _p(dh), _p(dz), z.numel(), code_of(z.dtype), _stream()), "m324_gelu_bwd")
+    _launch("m324_gelu_bwd", _p(z), _p(dh), _p(dz), z.numel(), code_of(z.dtype))
     return dz
 
 
@@ -1480,26 +1493,18 @@ def layernorm_bwd(x: torch.Tensor, w: torch.Tensor, eps: float, dy: torch.Tensor
     n_partial = min(512, (rows + 7) // 8)
     nb = 2 if cast_out is None else 3
     partial = torch.empty((n_partial, nb * Cdim), dtype=torch.float32, device=x.device)
-    gin, gout, off = row_map
-    if cast_out is None:
-        L.check(L.load().m324_layernorm_bwd(px, ldx, _vec(w, Cdim, "w"), eps, pdy, ldy, code_of(dy.dtype), pdx, lddx,
-                                            int(accumulate), _p(partial), n_partial, rows, Cdim, gin, gout, off, _stream()),
-                "m324_layernorm_bwd")
-        if not reduce:
-            return Rows(partial[:, :Cdim]), Rows(partial[:, Cdim:])
-        both = colsum(partial)
-        return both[:Cdim], both[Cdim:]
-    if cast_out.dtype != torch.bfloat16 or cast_out.shape != dx.shape:
-        raise L.M324Error("layernorm_bwd: cast_out must be a bf16 tensor shaped like dx")
-    pc, ldc = _rows(cast_out, "cast_out")
-    _wrote(cast_out)
-    L.check(L.load().m324_layernorm_bwd_cast(px, ldx, _vec(w, Cdim, "w"), eps, pdy, ldy, code_of(dy.dtype), pdx, lddx,
-                                             int(accumulate), _p(partial), n_partial, rows, Cdim, gin, gout, off, pc, ldc,
-                                             _stream()), "m324_layernorm_bwd_cast")
+    name, cast_args = "m324_layernorm_bwd", ()
+    if cast_out is not None:
+        if cast_out.dtype != torch.bfloat16 or cast_out.shape != dx.shape:
+            raise L.M324Error("layernorm_bwd: cast_out must be a bf16 tensor shaped like dx")
+        name, cast_args = "m324_layernorm_bwd_cast", _rows(cast_out, "cast_out")
+        _wrote(cast_out)
+    _launch(name, px, ldx, _vec(w, Cdim, "w"), eps, pdy, ldy, code_of(dy.dtype), pdx, lddx, int(accumulate), _p(partial), n_partial,
+            rows, Cdim, *row_map, *cast_args)
     if not reduce:
-        return Rows(partial[:, :Cdim]), Rows(partial[:, Cdim:2 * Cdim]), Rows(partial[:, 2 * Cdim:])
-    three = colsum(partial)
-    return three[:Cdim], three[Cdim:2 * Cdim], three[2 * Cdim:]
+        return tuple(Rows(partial[:, i * Cdim:(i + 1) * Cdim]) for i in range(nb))
+    sums = colsum(partial)
+    return tuple(sums[i * Cdim:(i + 1) * Cdim] for i in range(nb))
 
 
 def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1508,7 +1513,7 @@ def cast(x: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None
     if out is None:
         out = torch.empty((R, Cc), dtype=dtype, device=x.device)
     po, ldo = _rows(out, "out")
-    L.check(L.load().m324_cast(px, ld, code_of(x.dtype), po, ldo, code_of(out.dtype), R, Cc, _stream()), "m324_cast")
+    _launch("m324_cast", px, ld, code_of(x.dtype), po, ldo, code_of(out.dtype), R, Cc)
     return out
 
 
@@ -1518,7 +1523,7 @@ def attention_delta(O: torch.Tensor, dO: torch.Tensor, B: int, H: int, Lq: int) 
     if ld != ld2 or O.dtype != dO.dtype:
         raise L.M324Error("attention_delta: O and dO must share layout and dtype")
     D = torch.empty((B, H, Lq), dtype=torch.float32, device=O.device)
-    L.check(L.load().m324_attention_delta(po, pd, ld, _p(D), B, H, Lq, code_of(O.dtype), _stream()), "m324_attention_delta")
+    _launch("m324_attention_delta", po, pd, ld, _p(D), B, H, Lq, code_of(O.dtype))
     return D
 
 
@@ -1531,8 +1536,8 @@ def attention_bwd(Qs, K, V, dO, lse, D, *, shared_q: bool = False, scale: float 
             raise L.M324Error("attention_bwd: operands must be contiguous and share a dtype")
     dQ = torch.empty((B, H, Lq, 64), dtype=K.dtype, device=K.device)
     dK, dV = torch.empty_like(K), torch.empty_like(V)
-    L.check(L.load().m324_attention_bwd(_p(Qs), 0 if shared_q else H * Lq * 64, _p(K), _p(V), _p(dO), _p(lse), _p(D), _p(dQ),
-                                        _p(dK), _p(dV), B, H, Lq, Lk, scale, code_of(K.dtype), _stream()), "m324_attention_bwd")
+    _launch("m324_attention_bwd", _p(Qs), 0 if shared_q else H * Lq * 64, _p(K), _p(V), _p(dO), _p(lse), _p(D), _p(dQ),
+            _p(dK), _p(dV), B, H, Lq, Lk, scale, code_of(K.dtype))
     return dQ, dK, dV
 
 
@@ -1548,9 +1553,8 @@ def attention_bwd_mfma(spq: dict, spk: dict, spdo: dict, lse, D, *, shared_q: bo
         raise L.M324Error("attention_bwd_mfma is the bf16 kernel; use attention_bwd for fp32")
     dQ = torch.empty((B, H, Lq, 64), dtype=K.dtype, device=K.device)
     dK, dV = torch.empty_like(K), torch.empty_like(V)
-    L.check(L.load().m324_attention_bwd_mfma(_p(Qs), _p(Qst), 0 if shared_q else H * Lq * 64, 0 if shared_q else H * 64 * Lqp,
-                                             _p(K), _p(Kt), _p(V), _p(dO), _p(dOt), _p(lse), _p(D), _p(dQ), _p(dK), _p(dV),
-                                             B, H, Lq, Lk, scale, _stream()), "m324_attention_bwd_mfma")
+    _launch("m324_attention_bwd_mfma", _p(Qs), _p(Qst), 0 if shared_q else H * Lq * 64, 0 if shared_q else H * 64 * Lqp,
+            _p(K), _p(Kt), _p(V), _p(dO), _p(dOt), _p(lse), _p(D), _p(dQ), _p(dK), _p(dV), B, H, Lq, Lk, scale)
     return dQ, dK, dV
 
 
@@ -1569,9 +1573,8 @@ def qkv_split_bwd(dQ, dK, dV, q_raw, k_raw, q_w, k_w, eps: float, B: int, Lq: in
     poq, ldoq = rw(dq_out)
     pok, ldok = rw(dk_out)
     pov, ldov = rw(dv_out)
-    L.check(L.load().m324_qkv_split_bwd(_p(dQ), _p(dK), _p(dV), pq, ldq, pk, ldk, _vec(q_w, 64, "q_w"), _vec(k_w, 64, "k_w"),
-                                        eps, poq, ldoq, pok, ldok, pov, ldov, _p(partial), n_partial, B, Lq, H, code_of(dtype),
-                                        _stream()), "m324_qkv_split_bwd")
+    _launch("m324_qkv_split_bwd", _p(dQ), _p(dK), _p(dV), pq, ldq, pk, ldk, _vec(q_w, 64, "q_w"), _vec(k_w, 64, "k_w"),
+            eps, poq, ldoq, pok, ldok, pov, ldov, _p(partial), n_partial, B, Lq, H, code_of(dtype))
     if not reduce:                                          # ops.Rows: see layernorm_bwd
         return (Rows(partial[:, :64]) if (dQ is not None and q_w is not None) else None,
                 Rows(partial[:, 64:]) if (dK is not None and k_w is not None) else None)
@@ -1596,16 +1599,14 @@ def linear_n3_bwd(a: torch.Tensor, w: torch.Tensor, dout: torch.Tensor, mul_by: 
     dA = torch.empty((M, K), dtype=a.dtype, device=a.device)
     n_partial = min(1024, M)
     partial = torch.empty((n_partial, 3 * K), dtype=torch.float32, device=a.device)
-    L.check(L.load().m324_linear_n3_bwd(pa, lda, _p(w), _p(dout), _p(dA), K, _p(partial), n_partial, M, K, code_of(a.dtype), pm, ldm,
-                                        _stream()), "m324_linear_n3_bwd")
+    _launch("m324_linear_n3_bwd", pa, lda, _p(w), _p(dout), _p(dA), K, _p(partial), n_partial, M, K, code_of(a.dtype), pm, ldm)
     return dA, colsum(partial).reshape(3, K), colsum(dout)
 
 
 def mse_bwd(pred: torch.Tensor, target: torch.Tensor, weight: float, grad_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     pred, target = pred.contiguous().float(), target.contiguous().float()
     d = torch.empty_like(pred)
-    L.check(L.load().m324_mse_bwd(_p(pred), _p(target), _p(grad_scale), 2.0 * weight / pred.numel(), _p(d), pred.numel(),
-                                  _stream()), "m324_mse_bwd")
+    _launch("m324_mse_bwd", _p(pred), _p(target), _p(grad_scale), 2.0 * weight / pred.numel(), _p(d), pred.numel())
     return d
 
 
@@ -1614,8 +1615,7 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
             raise L.M324Error("adamw_step: tensors must be contiguous fp32 of equal size")
-    L.check(L.load().m324_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step,
-                                _p(grad_scale), _stream()), "m324_adamw")
+    _launch("m324_adamw", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, weight_decay, step, _p(grad_scale))
 
 
 def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n_decay: int, lr: float, beta1: float,
@@ -1624,8 +1624,7 @@ def adamw_flat(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
             raise L.M324Error("adamw_flat: tensors must be contiguous fp32 of equal size")
-    L.check(L.load().m324_adamw_flat(_p(p), _p(g), _p(m), _p(v), p.numel(), int(n_decay), lr, beta1, beta2, eps, weight_decay,
-                                     step, _p(grad_scale), _stream()), "m324_adamw_flat")
+    _launch("m324_adamw_flat", _p(p), _p(g), _p(m), _p(v), p.numel(), int(n_decay), lr, beta1, beta2, eps, weight_decay, step, _p(grad_scale))
 
 
 def weight_mirror(src: torch.Tensor, dst: torch.Tensor, dstT: Optional[torch.Tensor], table: torch.Tensor, n_items: int, n_tiles: int) -> None:
@@ -1634,9 +1633,8 @@ def weight_mirror(src: torch.Tensor, dst: torch.Tensor, dstT: Optional[torch.Ten
     if src.dtype != torch.float32 or dst.dtype != torch.bfloat16 or (dstT is not None and dstT.dtype != torch.bfloat16) or table.dtype != torch.uint8 \
             or table.numel() != n_items * C.sizeof(L.MirrorItem) or not table.is_cuda:
         raise L.M324Error("weight_mirror: fp32 source, bf16 copies and a device table of lib.MirrorItem records")
-    L.check(L.load().m324_weight_mirror(_p(src), _p(dst), _p(dstT), _p(table), n_items, n_tiles, _stream()), "m324_weight_mirror")
+    _launch("m324_weight_mirror", _p(src), _p(dst), _p(dstT), _p(table), n_items, n_tiles)
 
 
 def grad_sumsq(g: torch.Tensor, out: torch.Tensor, partial: torch.Tensor, sanitize: bool, accumulate: bool) -> None:
-    L.check(L.load().m324_grad_sumsq(_p(g), g.numel(), int(sanitize), _p(partial), _p(out), int(accumulate), _stream()),
-            "m324_grad_sumsq")
+    _launch("m324_grad_sumsq", _p(g), g.numel(), int(sanitize), _p(partial), _p(out), int(accumulate))

@@ -377,8 +377,8 @@ class QK_Norm_TransformerBlock(nn.Module):
             long_seq = L >= 2048
             Q, K = (torch.empty((B, a.num_heads, L, 64), dtype=P.dtype, device=x.device) for _ in range(2))
             V = torch.empty((B, a.num_heads, 64, L) if long_seq else (B, a.num_heads, L, 64), dtype=P.dtype, device=x.device)
-            proj(src, w, None, bias=bias, qkv_heads=(Q, K, V, qw, kw, RMS_EPS, ops.Q_PRESCALE, L, a.num_heads),
-                 **lnk(0, 3 * C))
+            heads = ops.QKVHeads(Q, K, V, q_w=qw, k_w=kw, eps=RMS_EPS, q_scale=ops.Q_PRESCALE, L=L, H=a.num_heads)
+            proj(src, w, None, bias=bias, qkv_heads=heads, **lnk(0, 3 * C))
             if rows_out is not None:
                 n_per, stride, first = rows_out
                 assert fold is not None and not long_seq and stride == L and first + n_per <= L
@@ -468,7 +468,7 @@ class QK_Norm_CrossAttentionBlock(nn.Module):
         if fuse_proj(P, B * Lq):                   # head-major Q (RMSNorm, pre-scale) straight from the projection's epilogue
             Q = torch.empty((B, a.num_heads, Lq, 64), dtype=P.dtype, device=query.device)
             ops.gemm(qn, P.mat(a.to_q.weight), None, bias=P.vec(a.to_q.bias),
-                     qkv_heads=(Q, None, None, qw, None, RMS_EPS, ops.Q_PRESCALE, Lq, a.num_heads))
+                     qkv_heads=ops.QKVHeads(Q, None, None, q_w=qw, k_w=None, eps=RMS_EPS, q_scale=ops.Q_PRESCALE, L=Lq, H=a.num_heads))
             return Q
         q = torch.empty(query.shape, dtype=P.dtype, device=query.device)
         ops.gemm(qn, P.mat(a.to_q.weight), q, bias=P.vec(a.to_q.bias))
@@ -486,7 +486,8 @@ class QK_Norm_CrossAttentionBlock(nn.Module):
         if fuse_proj(P, B * Lk) and Lk % 64 == 0:  # head-major K (RMSNorm) and the transposed, key-permuted Vt from the epilogue
             K = torch.empty((B, a.num_heads, Lk, 64), dtype=P.dtype, device=kv.device)
             Vt = torch.empty((B, a.num_heads, 64, Lk), dtype=P.dtype, device=kv.device)
-            ops.gemm(kn, w_kv, None, bias=b_kv, qkv_heads=(None, K, Vt, None, kw, RMS_EPS, 1.0, Lk, a.num_heads, True))
+            ops.gemm(kn, w_kv, None, bias=b_kv,
+                     qkv_heads=ops.QKVHeads(None, K, Vt, q_w=None, k_w=kw, eps=RMS_EPS, q_scale=1.0, L=Lk, H=a.num_heads, vt=True))
             return K, Vt
         kvp = torch.empty((B * Lk, 2 * a.dim), dtype=P.dtype, device=kv.device)
         ops.gemm(kn, w_kv, kvp, bias=b_kv)
@@ -515,9 +516,10 @@ class QK_Norm_CrossAttentionBlock(nn.Module):
         Vt = torch.empty((Bk, a.num_heads, 64, Lk), dtype=P.dtype, device=dev)
         w_kv, b_kv = P.cat_rows((a.to_k.weight, a.to_v.weight)), P.cat_vecs((a.to_k.bias, a.to_v.bias))
         pair: list = []
-        ops.gemm(qn, P.mat(a.to_q.weight), None, bias=P.vec(a.to_q.bias),
-                 qkv_heads=(Q, None, None, qw, None, RMS_EPS, ops.Q_PRESCALE, Lq, a.num_heads), defer=pair)
-        ops.gemm(kn, w_kv, None, bias=b_kv, qkv_heads=(None, K, Vt, None, kw, RMS_EPS, 1.0, Lk, a.num_heads, True), defer=pair)
+        ops.gemm(qn, P.mat(a.to_q.weight), None, bias=P.vec(a.to_q.bias), defer=pair,
+                 qkv_heads=ops.QKVHeads(Q, None, None, q_w=qw, k_w=None, eps=RMS_EPS, q_scale=ops.Q_PRESCALE, L=Lq, H=a.num_heads))
+        ops.gemm(kn, w_kv, None, bias=b_kv, defer=pair,
+                 qkv_heads=ops.QKVHeads(None, K, Vt, q_w=None, k_w=kw, eps=RMS_EPS, q_scale=1.0, L=Lk, H=a.num_heads, vt=True))
         ops.gemm_pair(pair)
         return Q, K, Vt
 
