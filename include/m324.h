@@ -590,6 +590,52 @@ int m324_render_shade(const int* faces, int n_faces, int n_vertices, int frames,
                       long normal_stride_t, const float* view, float ambient, int background, unsigned char* rgb, int* face, int* depth,
                       void* scratch, long scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Perceptual evaluation (csrc/perceptual.hip; added at ABI 23 without a bump): the pieces of LPIPS on a VGG16 trunk, what
+ * motion324_amd/perceptual.py strings together.  replaces: lpips.LPIPS(net='vgg', spatial=True) of the reference's
+ * evaluation/evaluation.py (torch / cuDNN there).  Everything is fp32, activations are NHWC ([images, H, W, C], C contiguous),
+ * every pointer is device memory and 16-byte aligned unless said otherwise, and images * H * W stays below 2^31.
+ *
+ * m324_conv3x3: out[i, y, x, n] = act(bias[n] + sum over taps t = 3 (dy + 1) + (dx + 1), dy, dx in -1..1, and channels c of
+ *   in[i, y + dy, x + dx, c] * wp[t * Cin + c][n]),  stride 1, a tap outside the image contributes 0 (zero padding of `in` itself),
+ *   act = max(., 0) when relu = 1, the identity when relu = 0.
+ *   Shape contract: Cin % 4 = 0, Cout % 32 = 0, both in 4 / 32 .. M324_CONV_MAX_CHANNELS; any H, W >= 1; any images >= 1.
+ *   wp: the weights repacked K-major, [Kpad, Cout] with row k = t * Cin + c and Kpad = 9 Cin rounded up to a multiple of
+ *   M324_CONV_KPAD; the rows from 9 Cin on are read and must hold zeros.  A 3-channel input is a 4-channel one whose fourth
+ *   channel and fourth weight rows are zero (m324_lpips_prepare writes that input).
+ *   Arithmetic: v_mfma_f32_32x32x2_f32, a sum in two levels.  r_j = the chain of fp32 fmas over k = j R .. min((j + 1) R, 9 Cin) - 1
+ *   in that order starting from 0, one rounding per product, R = M324_CONV_RUN; s = ((0 + r_0) + r_1) + ... in order; the
+ *   output is act(s + bias).  (One chain over all k loses accuracy with the length of the running sum: at 9 Cin = 4608 the
+ *   metric's deep layers came out up to 10 times further from fp64 than with runs of 144.)  An output's bits depend on its
+ *   9 Cin inputs and the weights alone: not on the image's place in the batch, the tile, the grid or a second call.
+ * m324_maxpool2x2: out[i, y, x, c] = max of in[i, 2y .. 2y + 1, 2x .. 2x + 1, c]; H and W even, C % 4 = 0.  Exact.
+ * m324_lpips_prepare: the scaled input of the trunk, dst fp32 [images, H, W, 4]:  dst_c = (x_c - shift_c) / scale_c for c < 3 with
+ *   shift (-.030, -.088, -.188), scale (.458, .448, .450), and dst_3 = 0.  mode M324_LPIPS_U8_NHWC: src uint8 [images, H, W, 3]
+ *   (any alignment), x = ((float)v / 255) * 2 - 1.  mode M324_LPIPS_F32_NCHW: src fp32 [images, 3, H, W] (4-byte aligned),
+ *   x = v, or v * 2 - 1 when normalize = 1.  Evaluated as written, nothing contracted: bytes and the floats built from them by
+ *   the same formula give the same bits.
+ * m324_lpips_layer: out[p] = (1 / pixels) sum over the pixels of sum_c w[c] (fa_c / (|fa| + 1e-10) - fb_c / (|fb| + 1e-10))^2
+ *   for pair p of fa, fb [pairs, pixels, channels], |f| = sqrt(sum_c f_c^2) over the pixel's channels; channels % 4 = 0,
+ *   <= M324_LPIPS_MAX_CHANNELS; pixels <= 2^24.  partial: scratch of pairs * M324_LPIPS_CHUNKS floats.  No atomics: a pair's
+ *   pixels are cut into min(M324_LPIPS_CHUNKS, ceil(pixels / 64)) equal runs, a workgroup sums one run in a fixed order, a second
+ *   kernel adds a pair's runs in order and divides.  The order depends on (pixels, channels) only -- not on pairs or p -- and
+ *   nothing is contracted, so swapping fa and fb gives the same bits and fa = fb gives exactly 0.
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_CONV_KPAD 16
+#define M324_CONV_RUN 144
+#define M324_CONV_MAX_CHANNELS 4096
+#define M324_LPIPS_U8_NHWC 0
+#define M324_LPIPS_F32_NCHW 1
+#define M324_LPIPS_MAX_CHANNELS 1024
+#define M324_LPIPS_CHUNKS 64
+int m324_conv3x3(const float* in, const float* wp, const float* bias, float* out, int images, int H, int W, int Cin, int Cout, int relu,
+                 void* stream);
+int m324_maxpool2x2(const float* in, float* out, int images, int H, int W, int C, void* stream);
+int m324_lpips_prepare(const void* src, int mode, int normalize, int images, int H, int W, float* dst, void* stream);
+int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs, long pixels, int channels, float* partial, float* out,
+                     void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

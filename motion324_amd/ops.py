@@ -1365,6 +1365,105 @@ def render_shade(faces: torch.Tensor, n_vertices: int, frames: int, size: int, s
     return rgb, face, depth
 
 
+# ------------------------------------------------------------------------------------------------ perceptual evaluation
+CONV_KPAD = 16                  # M324_CONV_KPAD: the packed weights have 9 Cin rows rounded up to this, zeros behind 9 Cin
+CONV_MAX_CHANNELS = 4096        # M324_CONV_MAX_CHANNELS
+LPIPS_MAX_CHANNELS = 1024       # M324_LPIPS_MAX_CHANNELS
+LPIPS_CHUNKS = 64               # M324_LPIPS_CHUNKS
+LPIPS_MODES = {"u8_nhwc": 0, "f32_nchw": 1}
+
+
+def conv_kpad(cin: int) -> int:
+    """rows of the K-major weight matrix m324_conv3x3 reads for `cin` input channels"""
+    return (9 * int(cin) + CONV_KPAD - 1) // CONV_KPAD * CONV_KPAD
+
+
+def _nhwc(x, name: str) -> torch.Tensor:
+    x = _device_array(x, torch.float32, name)
+    if x.dim() != 4 or 0 in x.shape or x.shape[3] % 4 or x.shape[3] > CONV_MAX_CHANNELS:
+        raise L.M324Error(f"{name}: expected fp32 NHWC [images,H,W,C] with C a multiple of 4 up to {CONV_MAX_CHANNELS}, got {tuple(x.shape)}")
+    if x.shape[0] * x.shape[1] * x.shape[2] >= 2 ** 31:
+        raise L.M324Error(f"{name}: images * H * W must stay below 2^31, got {tuple(x.shape)}")
+    return x
+
+
+def _out_like(out, shape, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not _is_device(out) or out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise L.M324Error(f"{name}: out must be a contiguous fp32 device tensor {tuple(shape)}")
+    return out
+
+
+def conv3x3(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3 x 3 convolution, stride 1, zero padding 1, bias and (relu) max(., 0) (m324_conv3x3, fp32 MFMA): x fp32 NHWC
+    [images,H,W,Cin], Cin % 4 = 0; wp fp32 [conv_kpad(Cin), Cout], row (3 (dy + 1) + dx + 1) * Cin + c, zeros behind 9 Cin
+    (perceptual.pack_conv_weight makes it); bias fp32 [Cout], Cout % 32 = 0.  Returns fp32 [images,H,W,Cout]."""
+    x = _nhwc(x, "conv3x3: x")
+    wp = _device_array(wp, torch.float32, "conv3x3: wp")
+    bias = _device_array(bias, torch.float32, "conv3x3: bias")
+    n, H, W, cin = x.shape
+    if wp.dim() != 2 or wp.shape[0] != conv_kpad(cin):
+        raise L.M324Error(f"conv3x3: wp must be [{conv_kpad(cin)},Cout] for Cin {cin}, got {tuple(wp.shape)}")
+    cout = wp.shape[1]
+    if cout % 32 or not 32 <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
+        raise L.M324Error(f"conv3x3: Cout must be a multiple of 32 up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, "
+                          f"bias {tuple(bias.shape)}")
+    out = _out_like(out, (n, H, W, cout), x.device, "conv3x3")
+    _launch("m324_conv3x3", _p(x), _p(wp), _p(bias), _p(out), n, H, W, cin, cout, 1 if relu else 0)
+    _wrote(out)
+    return out
+
+
+def maxpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """2 x 2, stride 2 max-pool of fp32 NHWC [images,H,W,C] with even H, W (m324_maxpool2x2) -> [images,H/2,W/2,C]"""
+    x = _nhwc(x, "maxpool2x2: x")
+    n, H, W, c = x.shape
+    if H % 2 or W % 2:
+        raise L.M324Error(f"maxpool2x2: H and W must be even, got {H} x {W}")
+    out = _out_like(out, (n, H // 2, W // 2, c), x.device, "maxpool2x2")
+    _launch("m324_maxpool2x2", _p(x), _p(out), n, H, W, c)
+    _wrote(out)
+    return out
+
+
+def lpips_prepare(src: torch.Tensor, *, normalize: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The trunk's scaled input fp32 [images,H,W,4] (channel 3 is zero) from uint8 [images,H,W,3] or fp32 [images,3,H,W] in
+    [-1, 1] -- in [0, 1] with normalize (m324_lpips_prepare; the formula is in include/m324.h)."""
+    _on_device(src, "lpips_prepare")
+    if src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and 0 not in src.shape:
+        mode, (n, H, W) = LPIPS_MODES["u8_nhwc"], src.shape[:3]
+        if normalize:
+            raise L.M324Error("lpips_prepare: normalize applies to fp32 input only; bytes are always 0..255")
+    elif src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] == 3 and 0 not in src.shape:
+        mode, (n, H, W) = LPIPS_MODES["f32_nchw"], (src.shape[0], src.shape[2], src.shape[3])
+    else:
+        raise L.M324Error(f"lpips_prepare: expected uint8 [images,H,W,3] or fp32 [images,3,H,W], got {src.dtype} {tuple(src.shape)}")
+    if n * H * W >= 2 ** 31:
+        raise L.M324Error(f"lpips_prepare: images * H * W must stay below 2^31, got {tuple(src.shape)}")
+    src = src.detach().contiguous()
+    out = _out_like(out, (n, H, W, 4), src.device, "lpips_prepare")
+    _launch("m324_lpips_prepare", _p(src), mode, 1 if normalize else 0, n, H, W, _p(out))
+    _wrote(out)
+    return out
+
+
+def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One LPIPS layer (m324_lpips_layer): fa, fb fp32 NHWC [pairs,H,W,C] taps of the two clips, w fp32 [C] the 1 x 1 layer;
+    returns fp32 [pairs], the mean over the pixels of sum_c w_c (n(fa)_c - n(fb)_c)^2.  Deterministic, symmetric in fa and fb."""
+    fa, fb = _nhwc(fa, "lpips_layer: fa"), _nhwc(fb, "lpips_layer: fb")
+    w = _device_array(w, torch.float32, "lpips_layer: w")
+    n, H, W, c = fa.shape
+    if fb.shape != fa.shape or tuple(w.shape) != (c,) or c > LPIPS_MAX_CHANNELS or H * W > 2 ** 24:
+        raise L.M324Error(f"lpips_layer: expected fa and fb of one shape [pairs,H,W,C], C <= {LPIPS_MAX_CHANNELS}, H * W <= 2^24, and w [C]; "
+                          f"got {tuple(fa.shape)}, {tuple(fb.shape)}, {tuple(w.shape)}")
+    out = _out_like(out, (n,), fa.device, "lpips_layer")
+    partial = torch.empty((n * LPIPS_CHUNKS,), dtype=torch.float32, device=fa.device)
+    _launch("m324_lpips_layer", _p(fa), _p(fb), _p(w), n, H * W, c, _p(partial), _p(out))
+    _wrote(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
