@@ -591,6 +591,63 @@ int m324_render_shade(const int* faces, int n_faces, int n_vertices, int frames,
                       void* scratch, long scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Textured and anti-aliased mesh clips (csrc/render.hip; added at ABI 23 without a bump): a mip-mapped base-colour texture
+ * addressed through per-corner UVs, and ss x ss supersampling resolved inside the shading kernel.  replaces: the textured
+ * Blender render of the reference's utils/render.py.  The four entry points above are untouched.  The arithmetic below IS the
+ * contract, as above: integers for the chain and the resolve, uncontracted fp32 with correctly rounded division elsewhere.
+ *
+ * Why the level is exact: the camera is orthographic and UVs interpolate affinely over a triangle, so the texel footprint of a
+ * sample is the same everywhere on a (frame, face).  One level per (frame, face) is therefore the true isotropic level, and it
+ * is chosen by comparing against powers of two, which fp32 represents exactly.
+ *
+ * The chain (m324_texture_plan, m324_texture_mips).  Sides 1 <= tex_h, tex_w <= M324_TEXTURE_MAX_SIDE.  Level 0 is the texture;
+ *   W_(l+1) = max(1, W_l >> 1), H_(l+1) = max(1, H_l >> 1); the last level is 1 x 1, so levels = floor(log2(max(W_0, H_0))) + 1
+ *   <= M324_TEXTURE_MAX_LEVELS.  A texel is 4 bytes (R, G, B, 0): one tap is one 32-bit load.  Level l is row-major [H_l, W_l]
+ *   at byte offset off_l of `mips`:  off_0 = 0,  off_(l+1) = off_l + roundup(4 * W_l * H_l, 256);  the chain's size is off_levels.
+ *   The bytes between the end of a level and the next 256-byte boundary are never read or written.
+ *   m324_texture_plan: host-only; stores the level count in *levels and the chain's bytes in *bytes (either may be NULL).
+ *   m324_texture_mips: texels uint8 [tex_h, tex_w, channels], channels 3 or 4 (a fourth channel is ignored), device memory;
+ *   mips device memory, 4-byte aligned, mips_bytes >= the plan's bytes.  Level 0 is the texture's R, G, B and a zero byte.
+ *   Texel (x, y) of level l + 1, per channel:  (a + b + c + d + 2) >> 2  over level l at columns min(2 x, W_l - 1) and
+ *   min(2 x + 1, W_l - 1), rows min(2 y, H_l - 1) and min(2 y + 1, H_l - 1), in integers.  W_(l+1) = W_l >> 1 never reaches an
+ *   odd last column (or row) of level l: it is dropped; the min() only acts where a side of level l is already 1.
+ *   One launch for level 0 and one per further level, in order, on `stream`.
+ *
+ * m324_render_shade_tex: m324_render_shade with an optional texture and supersampling.  `size` is the SAMPLE resolution S' that
+ *   m324_render_project and m324_render_raster ran at (same scratch, same order, same stream); supersample = ss in {1, 2, 4},
+ *   S' % ss == 0, S' <= M324_RENDER_MAX_SIDE.  Outputs, each skipped when NULL (not all three): rgb uint8 [frames, S'/ss, S'/ss, 3];
+ *   face and depth int32 [frames, S', S'], one value per sample, exactly m324_render_shade's.
+ *   face_uvs fp32 [n_faces, 3, 2] (corner k of face f at + 6 f + 2 k: u, v), device, or NULL; mips = the chain of a
+ *   tex_h x tex_w texture (m324_texture_plan bytes, 4-byte aligned).  face_uvs and mips are given together or both NULL (then
+ *   tex_h = tex_w = 0), and never together with colors.  use_mips = 0: always level 0.
+ *   Per sample everything is m324_render_shade's arithmetic, except the albedo when face_uvs is given:
+ *   1. corner UVs (u_k, v_k) of the owning face; a non-finite component is replaced by 0.
+ *   2. u = (b_0 * u_0 + b_1 * u_1) + b_2 * u_2, and the same for v; a non-finite u or v (overflow) is replaced by 0.
+ *   3. level: ua2 = |(u_1 - u_0) * (v_2 - v_0) - (u_2 - u_0) * (v_1 - v_0)|;
+ *      rho = ((ua2 * (float)W_0) * (float)H_0) / ((float)|area2| / 256.0f)  -- area2 is the frame's integer doubled area in 1/16
+ *      pixel units, so rho is texels per sample;  l = 0; while (l < levels - 1 && rho > 2 * 4^l) ++l;  the nearest level: a NaN
+ *      stays at 0 and +inf goes to the last level.  With use_mips = 0, l = 0.
+ *   4. wrap (repeat): uw = u - floorf(u), vw = v - floorf(v);  x = uw * (float)W_l - 0.5f;  y = (1.0f - vw) * (float)H_l - 0.5f
+ *      (row 0 is the image's top and v points up, the convention of m324_surface_sample's uv).
+ *   5. bilinear: x0 = floorf(x), fx = x - x0; columns x0 mod W_l and (x0 + 1) mod W_l, taken non-negative; rows the same from y.
+ *      Per channel on (float)byte, t_rc the tap at row r, column c of the pair:  top = t00 + fx * (t01 - t00);
+ *      bot = t10 + fx * (t11 - t10);  val = top + fy * (bot - top);  albedo = val / 255.0f.  Bytes are used as they are (no
+ *      sRGB decode), like colors and the samplers.
+ *   Resolve: the byte of an output pixel is (sum over its ss x ss samples of the sample's byte + ss * ss / 2) >> log2(ss * ss) per
+ *   channel; a background sample contributes the background byte.  One lane per output pixel walks its samples: no S' x S'
+ *   colour buffer exists.  With face_uvs NULL and ss = 1 the three outputs equal m324_render_shade's bit for bit.
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_TEXTURE_MAX_SIDE 16384
+#define M324_TEXTURE_MAX_LEVELS 15
+int m324_texture_plan(int tex_h, int tex_w, int* levels, long* bytes);
+int m324_texture_mips(const unsigned char* texels, int tex_h, int tex_w, int channels, void* mips, long mips_bytes, void* stream);
+int m324_render_shade_tex(const int* faces, int n_faces, int n_vertices, int frames, int size, const float* colors, const float* normals,
+                          long normal_stride_t, const float* view, float ambient, int background, const float* face_uvs,
+                          const void* mips, int tex_h, int tex_w, int use_mips, int supersample, unsigned char* rgb, int* face,
+                          int* depth, void* scratch, long scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Perceptual evaluation (csrc/perceptual.hip; added at ABI 23 without a bump): the pieces of LPIPS on a VGG16 trunk, what
  * motion324_amd/perceptual.py strings together.  replaces: lpips.LPIPS(net='vgg', spatial=True) of the reference's
  * evaluation/evaluation.py (torch / cuDNN there).  Everything is fp32, activations are NHWC ([images, H, W, C], C contiguous),

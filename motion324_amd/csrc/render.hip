@@ -6,7 +6,8 @@
 // picks the triangle owning a pixel is made in integers -- snapped subpixel vertices, int64 edge functions, an orientation-free
 // top-left rule, an integer depth -- and ownership is settled by a 64-bit atomic min over (depth, face index).  Min commutes, so
 // the result depends on no arrival order, grid shape, CU count or queue order.  The fp32 part (projection, barycentrics, shading)
-// is compiled without contraction and divides / takes roots with the correctly rounded intrinsics.
+// is compiled without contraction and divides / takes roots with the correctly rounded intrinsics.  The second half of the file
+// adds a mip-mapped texture and supersampling under the same rules (m324_texture_*, m324_render_shade_tex).
 #include "common.h"
 #include <math.h>
 
@@ -343,5 +344,332 @@ extern "C" int m324_render_shade(const int* faces, int n_faces, int n_vertices, 
         hipLaunchKernelGGL(render_shade_kernel<false>, grid, block, 0, (hipStream_t)stream, faces, n_faces, n_vertices, total, size, keys, proj, pos, colors,
                            normals, normal_stride_t, m, ambient, bg0, bg1, bg2, rgb, face, depth);
     M324_CHECK_LAUNCH("m324_render_shade");
+    return M324_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ textures and supersampling
+// A mip-mapped base-colour texture addressed through per-corner UVs, and ss x ss samples per output pixel resolved by the lane
+// that shades them (include/m324.h, "Textured and anti-aliased mesh clips").  The camera is orthographic and UVs interpolate
+// affinely, so one level per (frame, face) is the exact isotropic level; it is picked by comparisons against powers of two.
+namespace {
+
+// The chain of a texture, passed to the kernels by value: off[l] is level l's offset in 32-bit texels, off[levels] the end.
+struct Chain {
+    long off[M324_TEXTURE_MAX_LEVELS + 1];
+    int levels, w0, h0;
+};
+
+inline Chain chain_of(int tex_h, int tex_w) {
+    Chain c;
+    c.w0 = tex_w;
+    c.h0 = tex_h;
+    long at = 0;
+    int w = tex_w, h = tex_h, l = 0;
+    for (;; ++l) {
+        c.off[l] = at / 4;
+        at += round_up(4L * w * h);
+        if (w == 1 && h == 1) break;
+        w = w > 1 ? w >> 1 : 1;
+        h = h > 1 ? h >> 1 : 1;
+    }
+    c.levels = l + 1;
+    for (int k = c.levels; k <= M324_TEXTURE_MAX_LEVELS; ++k) c.off[k] = at / 4;
+    return c;
+}
+
+int check_texture(const char* who, int tex_h, int tex_w) {
+    M324_REQUIRE(tex_h >= 1 && tex_h <= M324_TEXTURE_MAX_SIDE && tex_w >= 1 && tex_w <= M324_TEXTURE_MAX_SIDE,
+                 "%s: texture sides must be in 1..%d, got %d x %d", who, M324_TEXTURE_MAX_SIDE, tex_h, tex_w);
+    return M324_OK;
+}
+
+// One lane = one texel of level 0: R, G, B and a zero byte.
+__global__ __launch_bounds__(THREADS) void texture_pack_kernel(const unsigned char* __restrict__ texels, long total, int channels,
+                                                               unsigned* __restrict__ out) {
+    const long g = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (g >= total) return;
+    const unsigned char* p = texels + g * channels;
+    out[g] = (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
+}
+
+// One lane = one texel of level l + 1: the rounded mean of a 2 x 2 block of level l, per byte.
+__global__ __launch_bounds__(THREADS) void texture_down_kernel(const unsigned* __restrict__ src, int sw, int sh, unsigned* __restrict__ dst,
+                                                               int dw, long total) {
+    const long g = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (g >= total) return;
+    const int x = (int)(g % dw), y = (int)(g / dw);
+    const int x0 = min(2 * x, sw - 1), x1 = min(2 * x + 1, sw - 1), y0 = min(2 * y, sh - 1), y1 = min(2 * y + 1, sh - 1);
+    const unsigned a = src[(long)y0 * sw + x0], b = src[(long)y0 * sw + x1], c = src[(long)y1 * sw + x0], d = src[(long)y1 * sw + x1];
+    unsigned out = 0;
+#pragma unroll
+    for (int k = 0; k < 24; k += 8) out |= ((((a >> k) & 255u) + ((b >> k) & 255u) + ((c >> k) & 255u) + ((d >> k) & 255u) + 2u) >> 2) << k;
+    dst[g] = out;
+}
+
+// What a lane keeps of the face that owns its current sample; rebuilt only when the next sample belongs to another face.
+struct FaceState {
+    Tri t;
+    long i[3];
+    float area;
+    float shade;                                         // flat shading: constant over the face
+    float u[3], v[3];                                    // corner UVs, non-finite components replaced by 0
+    int lw, lh;                                          // the level's sides
+    long loff;                                           // and its offset in texels
+};
+
+template <bool SMOOTH, bool TEX>
+__device__ __forceinline__ void face_setup(FaceState& s, int face, const int* __restrict__ faces, int n_vertices, const float* __restrict__ pos_t,
+                                           float ambient, const float* __restrict__ face_uvs, const Chain& chain, int last) {
+    s.i[0] = faces[(long)face * 3];
+    s.i[1] = faces[(long)face * 3 + 1];
+    s.i[2] = faces[(long)face * 3 + 2];
+    s.area = (float)(double)s.t.area2;                   // |values| < 2^53: exact in fp64, so one rounding to fp32
+    if (!SMOOTH) {
+        float e1[3], e2[3], n[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            e1[c] = pos_t[s.i[1] * 3 + c] - pos_t[s.i[0] * 3 + c];
+            e2[c] = pos_t[s.i[2] * 3 + c] - pos_t[s.i[0] * 3 + c];
+        }
+        n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        const float len = __fsqrt_rn((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+        const float l = (len > 0.f && finitef(len)) ? __fdiv_rn(fabsf(n[2]), len) : 0.f;
+        s.shade = ambient + (1.0f - ambient) * l;
+    }
+    if (TEX) {
+        const float* uv = face_uvs + (long)face * 6;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float a = uv[2 * k], b = uv[2 * k + 1];
+            s.u[k] = finitef(a) ? a : 0.f;
+            s.v[k] = finitef(b) ? b : 0.f;
+        }
+        const float ua2 = fabsf((s.u[1] - s.u[0]) * (s.v[2] - s.v[0]) - (s.u[2] - s.u[0]) * (s.v[1] - s.v[0]));
+        const float rho = __fdiv_rn((ua2 * (float)chain.w0) * (float)chain.h0, s.area / 256.0f);
+        // while (l < last && rho > 2 * 4^l) ++l, unrolled: the condition is monotone in l, so the highest level whose test
+        // passes is where the loop stops.  Constant indices keep the offsets in the kernel's arguments (no table in memory).
+        int l = 0;
+        long off = chain.off[0];
+        float threshold = 2.0f;
+#pragma unroll
+        for (int k = 1; k < M324_TEXTURE_MAX_LEVELS; ++k) {
+            if (k <= last && rho > threshold) {
+                l = k;
+                off = chain.off[k];
+            }
+            threshold *= 4.0f;                           // a power of two: exact
+        }
+        s.lw = max(chain.w0 >> l, 1);
+        s.lh = max(chain.h0 >> l, 1);
+        s.loff = off;
+    }
+}
+
+// One lane = one OUTPUT pixel of one frame: it walks its ss x ss samples, shades each as render_shade_kernel does (the albedo
+// from the texture when TEX), writes the samples' face and depth, and stores the rounded mean of their bytes.
+template <bool SMOOTH, bool TEX>
+__global__ __launch_bounds__(THREADS) void render_shade_tex_kernel(const int* __restrict__ faces, int n_faces, int n_vertices, long total, int size,
+                                                                   int ss, const unsigned long long* __restrict__ keys,
+                                                                   const int4* __restrict__ proj, const float* __restrict__ pos,
+                                                                   const float* __restrict__ colors, const float* __restrict__ normals,
+                                                                   long normal_stride_t, View view, float ambient, int bg0, int bg1, int bg2,
+                                                                   const float* __restrict__ face_uvs, const unsigned* __restrict__ mips,
+                                                                   Chain chain, int last, unsigned char* __restrict__ rgb,
+                                                                   int* __restrict__ face_out, int* __restrict__ depth_out) {
+    const long g = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (g >= total) return;
+    const int so = size / ss;
+    const long out_pixels = (long)so * so;
+    const long frame = g / out_pixels;
+    const int at = (int)(g % out_pixels), oy = at / so, ox = at % so;
+    const int4* proj_t = proj + frame * n_vertices;
+    const float* pos_t = pos + frame * n_vertices * 3;
+    const long sample0 = frame * size * size;
+    FaceState s;
+    int current = -1;                                    // the face s describes
+    int sum[3] = {0, 0, 0};
+    for (int sy = 0; sy < ss; ++sy) {
+        for (int sx = 0; sx < ss; ++sx) {
+            const int px = ox * ss + sx, py = oy * ss + sy;
+            const long at_s = sample0 + (long)py * size + px;
+            const unsigned long long key = keys[at_s];
+            int face = -1, depth = -1;
+            int out[3] = {bg0, bg1, bg2};
+            bool owned = key != EMPTY_KEY && (key & 0xffffffffULL) < (unsigned long long)n_faces;
+            if (owned) {
+                const int f = (int)(key & 0xffffffffULL);
+                if (f != current) {
+                    owned = setup_tri(faces, (long)f, n_vertices, proj_t, size, s.t);
+                    current = -1;
+                    if (owned) {
+                        face_setup<SMOOTH, TEX>(s, f, faces, n_vertices, pos_t, ambient, face_uvs, chain, last);
+                        current = f;
+                    }
+                }
+            }
+            if (owned) {
+                face = current;
+                depth = (int)(key >> 32);
+                const long long X = 16 * px + 8, Y = 16 * py + 8;
+                float b[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) b[k] = __fdiv_rn((float)(double)(s.t.A[k] * X + s.t.B[k] * Y + s.t.C[k]), s.area);
+                float shade = SMOOTH ? 0.f : s.shade;
+                if (SMOOTH) {
+                    const float* vn = normals + frame * normal_stride_t;
+                    float m[3], n[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) m[c] = (b[0] * vn[s.i[0] * 3 + c] + b[1] * vn[s.i[1] * 3 + c]) + b[2] * vn[s.i[2] * 3 + c];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) n[r] = (view.m[r * 4] * m[0] + view.m[r * 4 + 1] * m[1]) + view.m[r * 4 + 2] * m[2];
+                    const float len = __fsqrt_rn((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+                    const float l = (len > 0.f && finitef(len)) ? __fdiv_rn(fabsf(n[2]), len) : 0.f;
+                    shade = ambient + (1.0f - ambient) * l;
+                }
+                unsigned t00 = 0, t01 = 0, t10 = 0, t11 = 0;
+                float fx = 0.f, fy = 0.f;
+                if (TEX) {
+                    float u = (b[0] * s.u[0] + b[1] * s.u[1]) + b[2] * s.u[2];
+                    float v = (b[0] * s.v[0] + b[1] * s.v[1]) + b[2] * s.v[2];
+                    u = finitef(u) ? u : 0.f;
+                    v = finitef(v) ? v : 0.f;
+                    const float uw = u - floorf(u), vw = v - floorf(v);          // in [0, 1]
+                    const float x = uw * (float)s.lw - 0.5f, y = (1.0f - vw) * (float)s.lh - 0.5f;
+                    const float xf = floorf(x), yf = floorf(y);                  // in [-1, side - 1]
+                    fx = x - xf;
+                    fy = y - yf;
+                    const int x0 = (int)xf, y0 = (int)yf;
+                    int c0 = x0 < 0 ? x0 + s.lw : x0, c1 = x0 + 1 >= s.lw ? x0 + 1 - s.lw : x0 + 1;
+                    int r0 = y0 < 0 ? y0 + s.lh : y0, r1 = y0 + 1 >= s.lh ? y0 + 1 - s.lh : y0 + 1;
+                    // the ranges above already hold; the clamps keep every tap inside the level whatever the arithmetic did
+                    c0 = min(max(c0, 0), s.lw - 1);
+                    c1 = min(max(c1, 0), s.lw - 1);
+                    r0 = min(max(r0, 0), s.lh - 1);
+                    r1 = min(max(r1, 0), s.lh - 1);
+                    const unsigned* level = mips + s.loff;
+                    t00 = level[(long)r0 * s.lw + c0];
+                    t01 = level[(long)r0 * s.lw + c1];
+                    t10 = level[(long)r1 * s.lw + c0];
+                    t11 = level[(long)r1 * s.lw + c1];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float albedo;
+                    if (TEX) {
+                        const float a00 = (float)((t00 >> (8 * c)) & 255u), a01 = (float)((t01 >> (8 * c)) & 255u);
+                        const float a10 = (float)((t10 >> (8 * c)) & 255u), a11 = (float)((t11 >> (8 * c)) & 255u);
+                        const float top = a00 + fx * (a01 - a00);
+                        const float bot = a10 + fx * (a11 - a10);
+                        albedo = __fdiv_rn(top + fy * (bot - top), 255.0f);
+                    } else {
+                        albedo = colors ? (b[0] * colors[s.i[0] * 3 + c] + b[1] * colors[s.i[1] * 3 + c]) + b[2] * colors[s.i[2] * 3 + c] : 0.8f;
+                    }
+                    float v = albedo * shade;
+                    v = v > 0.f ? v : 0.f;               // a NaN counts as 0
+                    v = v < 1.f ? v : 1.f;
+                    out[c] = (int)floorf(v * 255.f + 0.5f);
+                }
+            }
+            sum[0] += out[0];
+            sum[1] += out[1];
+            sum[2] += out[2];
+            if (face_out) face_out[at_s] = face;
+            if (depth_out) depth_out[at_s] = depth;
+        }
+    }
+    if (rgb) {
+        const int half = (ss * ss) >> 1, shift = ss == 1 ? 0 : (ss == 2 ? 2 : 4);
+        rgb[g * 3] = (unsigned char)((sum[0] + half) >> shift);
+        rgb[g * 3 + 1] = (unsigned char)((sum[1] + half) >> shift);
+        rgb[g * 3 + 2] = (unsigned char)((sum[2] + half) >> shift);
+    }
+}
+
+}  // namespace
+
+extern "C" int m324_texture_plan(int tex_h, int tex_w, int* levels, long* bytes) {
+    const int rc = check_texture("m324_texture_plan", tex_h, tex_w);
+    if (rc != M324_OK) return rc;
+    const Chain c = chain_of(tex_h, tex_w);
+    if (levels) *levels = c.levels;
+    if (bytes) *bytes = c.off[c.levels] * 4;
+    return M324_OK;
+}
+
+extern "C" int m324_texture_mips(const unsigned char* texels, int tex_h, int tex_w, int channels, void* mips, long mips_bytes, void* stream) {
+    M324_REQUIRE(texels && mips, "m324_texture_mips: null texels or mips");
+    const int rc = check_texture("m324_texture_mips", tex_h, tex_w);
+    if (rc != M324_OK) return rc;
+    M324_REQUIRE(channels == 3 || channels == 4, "m324_texture_mips: channels must be 3 or 4, got %d", channels);
+    const Chain c = chain_of(tex_h, tex_w);
+    M324_REQUIRE(mips_bytes >= c.off[c.levels] * 4, "m324_texture_mips: needs %ld mips bytes (m324_texture_plan), got %ld", c.off[c.levels] * 4, mips_bytes);
+    M324_REQUIRE(((uintptr_t)mips & 3) == 0, "m324_texture_mips: mips must be 4-byte aligned");
+    unsigned* base = (unsigned*)mips;
+    hipStream_t st = (hipStream_t)stream;
+    long total = (long)tex_h * tex_w;
+    hipLaunchKernelGGL(texture_pack_kernel, dim3(ceil_div(total, THREADS)), dim3(THREADS), 0, st, texels, total, channels, base);
+    int w = tex_w, h = tex_h;
+    for (int l = 0; l + 1 < c.levels; ++l) {
+        const int dw = w > 1 ? w >> 1 : 1, dh = h > 1 ? h >> 1 : 1;
+        total = (long)dw * dh;
+        hipLaunchKernelGGL(texture_down_kernel, dim3(ceil_div(total, THREADS)), dim3(THREADS), 0, st, base + c.off[l], w, h, base + c.off[l + 1], dw, total);
+        w = dw;
+        h = dh;
+    }
+    M324_CHECK_LAUNCH("m324_texture_mips");
+    return M324_OK;
+}
+
+extern "C" int m324_render_shade_tex(const int* faces, int n_faces, int n_vertices, int frames, int size, const float* colors, const float* normals,
+                                     long normal_stride_t, const float* view, float ambient, int background, const float* face_uvs,
+                                     const void* mips, int tex_h, int tex_w, int use_mips, int supersample, unsigned char* rgb, int* face,
+                                     int* depth, void* scratch, long scratch_bytes, void* stream) {
+    M324_REQUIRE(scratch && view && (faces || n_faces == 0), "m324_render_shade_tex: null faces, view or scratch");
+    M324_REQUIRE(rgb || face || depth, "m324_render_shade_tex: null rgb, face and depth: nothing to write");
+    int rc = check_sizes("m324_render_shade_tex", n_vertices, n_faces, frames, size);
+    if (rc != M324_OK) return rc;
+    M324_REQUIRE(normal_stride_t >= 0 && ambient >= 0.f && ambient <= 1.f && background >= 0 && background <= 0xffffff,
+                 "m324_render_shade_tex: need normal_stride_t >= 0, ambient in [0, 1], background = 0xBBGGRR (normal_stride_t=%ld ambient=%g background=%d)",
+                 normal_stride_t, (double)ambient, background);
+    M324_REQUIRE(supersample == 1 || supersample == 2 || supersample == 4, "m324_render_shade_tex: supersample must be 1, 2 or 4, got %d", supersample);
+    M324_REQUIRE(size % supersample == 0, "m324_render_shade_tex: size (the sample resolution, %d) must be a multiple of supersample (%d)", size, supersample);
+    M324_REQUIRE((face_uvs != nullptr) == (mips != nullptr), "m324_render_shade_tex: face_uvs and mips go together (a texture needs UVs, UVs need a texture)");
+    Chain chain = {};
+    if (face_uvs) {
+        M324_REQUIRE(!colors, "m324_render_shade_tex: a texture and colors are two albedos: give one");
+        rc = check_texture("m324_render_shade_tex", tex_h, tex_w);
+        if (rc != M324_OK) return rc;
+        M324_REQUIRE(((uintptr_t)mips & 3) == 0, "m324_render_shade_tex: mips must be 4-byte aligned");
+        chain = chain_of(tex_h, tex_w);
+    } else {
+        M324_REQUIRE(tex_h == 0 && tex_w == 0, "m324_render_shade_tex: a texture size (%d x %d) without face_uvs and mips", tex_h, tex_w);
+    }
+    const Layout l = layout_of(n_vertices, n_faces, frames, size);
+    rc = check_scratch("m324_render_shade_tex", l, scratch, scratch_bytes);
+    if (rc != M324_OK) return rc;
+    View m;
+    for (int i = 0; i < 12; ++i) m.m[i] = view[i];
+    char* base = (char*)scratch;
+    const int so = size / supersample;
+    const long total = (long)frames * so * so;
+    const dim3 grid(ceil_div(total, THREADS)), block(THREADS);
+    const unsigned long long* keys = (const unsigned long long*)(base + l.keys);
+    const int4* proj = (const int4*)(base + l.proj);
+    const float* pos = (const float*)(base + l.view);
+    const int bg0 = background & 255, bg1 = (background >> 8) & 255, bg2 = (background >> 16) & 255;
+    const int last = (face_uvs && use_mips) ? chain.levels - 1 : 0;
+    const unsigned* tex = (const unsigned*)mips;
+    hipStream_t st = (hipStream_t)stream;
+#define M324_SHADE_TEX(SMOOTH, TEX)                                                                                                              \
+    hipLaunchKernelGGL((render_shade_tex_kernel<SMOOTH, TEX>), grid, block, 0, st, faces, n_faces, n_vertices, total, size, supersample, keys, proj, \
+                       pos, colors, normals, normal_stride_t, m, ambient, bg0, bg1, bg2, face_uvs, tex, chain, last, rgb, face, depth)
+    if (normals && face_uvs) M324_SHADE_TEX(true, true);
+    else if (normals) M324_SHADE_TEX(true, false);
+    else if (face_uvs) M324_SHADE_TEX(false, true);
+    else M324_SHADE_TEX(false, false);
+#undef M324_SHADE_TEX
+    M324_CHECK_LAUNCH("m324_render_shade_tex");
     return M324_OK;
 }

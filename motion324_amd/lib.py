@@ -113,6 +113,9 @@ SIGNATURES = {
     "m324_render_project": [_P, _L, _I, _I, _I, _P, _I, _P, _L, _P],
     "m324_render_raster": [_P, _I, _I, _I, _I, _I, _P, _L, _P],
     "m324_render_shade": [_P, _I, _I, _I, _I, _P, _P, _L, _P, _F, _I, _P, _P, _P, _P, _L, _P],
+    "m324_texture_plan": [_I, _I, _P, _P],
+    "m324_texture_mips": [_P, _I, _I, _I, _P, _L, _P],
+    "m324_render_shade_tex": [_P, _I, _I, _I, _I, _P, _P, _L, _P, _F, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P],
     "m324_conv3x3": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "m324_maxpool2x2": [_P, _P, _I, _I, _I, _I, _P],
     "m324_lpips_prepare": [_P, _I, _I, _I, _I, _I, _P, _P],

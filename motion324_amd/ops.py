@@ -1365,6 +1365,110 @@ def render_shade(faces: torch.Tensor, n_vertices: int, frames: int, size: int, s
     return rgb, face, depth
 
 
+TEXTURE_MAX_SIDE = 16384        # M324_TEXTURE_MAX_SIDE
+SUPERSAMPLES = (1, 2, 4)
+
+
+def texture_plan(tex_h: int, tex_w: int):
+    """(levels, bytes) of the mip chain of a tex_h x tex_w texture: m324_texture_plan, host-only"""
+    levels, need = C.c_int(0), C.c_long(0)
+    L.check(L.load().m324_texture_plan(int(tex_h), int(tex_w), C.addressof(levels), C.addressof(need)), "m324_texture_plan")
+    return int(levels.value), int(need.value)
+
+
+def texture_levels(tex_h: int, tex_w: int):
+    """[(byte offset, H_l, W_l)] of every level, by the offset rule of include/m324.h; its length and end are the plan's"""
+    count, need = texture_plan(tex_h, tex_w)
+    out, at, h, w = [], 0, int(tex_h), int(tex_w)
+    while True:
+        out.append((at, h, w))
+        at += (4 * w * h + 255) // 256 * 256
+        if h == 1 and w == 1:
+            break
+        h, w = max(1, h >> 1), max(1, w >> 1)
+    if len(out) != count or at != need:
+        raise L.M324Error(f"texture_levels: {len(out)} levels / {at} bytes by the offset rule, m324_texture_plan says {count} / {need}")
+    return out
+
+
+def _texture(texture, name: str) -> torch.Tensor:
+    _on_device(texture, name)
+    if texture.dtype != torch.uint8 or texture.dim() != 3 or texture.shape[2] not in (3, 4) or 0 in texture.shape:
+        raise L.M324Error(f"{name}: expected a uint8 texture [H,W,3] or [H,W,4], got {texture.dtype} {tuple(texture.shape)}")
+    if max(texture.shape[0], texture.shape[1]) > TEXTURE_MAX_SIDE:
+        raise L.M324Error(f"{name}: texture sides must be in 1..{TEXTURE_MAX_SIDE}, got {texture.shape[0]} x {texture.shape[1]}")
+    return texture.detach().contiguous()
+
+
+def texture_mips(texture: torch.Tensor):
+    """The mip chain of a uint8 device texture [H,W,3|4] (m324_texture_mips; a fourth channel is ignored): (mips uint8 [bytes],
+    levels = texture_levels(H, W)).  Level l is mips[off : off + 4 H_l W_l] viewed as [H_l, W_l, 4], texels (R, G, B, 0)."""
+    tex = _texture(texture, "texture_mips")
+    H, W, ch = tex.shape
+    levels = texture_levels(H, W)
+    need = texture_plan(H, W)[1]
+    mips = torch.zeros((need,), dtype=torch.uint8, device=tex.device)
+    _launch("m324_texture_mips", _p(tex), H, W, ch, _p(mips), need)
+    _wrote(mips)
+    return mips, levels
+
+
+def render_shade_tex(faces: torch.Tensor, n_vertices: int, frames: int, size: int, scratch: torch.Tensor, view, *,
+                     colors: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None, ambient: float = 0.3,
+                     background=(0, 0, 0), face_uvs: Optional[torch.Tensor] = None, mips: Optional[torch.Tensor] = None,
+                     tex_size=None, use_mips: bool = True, supersample: int = 1, out=None, faces_checked: bool = False):
+    """render_shade with an optional texture and supersampling (m324_render_shade_tex).  `size` is the sample resolution S' that
+    render_project and render_raster ran at; rgb is uint8 [T,S'/ss,S'/ss,3], face and depth stay int32 [T,S',S'].  face_uvs
+    fp32 [F,3,2] with mips and tex_size = (H, W) of texture_mips select the textured albedo; use_mips False samples level 0."""
+    _on_device(scratch, "render_shade_tex")
+    dev = scratch.device
+    T, S, nv, ss = int(frames), int(size), int(n_vertices), int(supersample)
+    if ss not in SUPERSAMPLES or S % ss:
+        raise L.M324Error(f"render_shade_tex: supersample must be one of {SUPERSAMPLES} and divide size, got {supersample!r} at size {S}")
+    f = _render_faces(faces, nv, dev, "render_shade_tex", faces_checked)
+    m = _render_view(view, "render_shade_tex")
+    need = render_plan(nv, f.shape[0], T, S)
+    scratch = _render_scratch(scratch, need, dev, "render_shade_tex")
+    col = None
+    if colors is not None:
+        col = _device_array(colors, torch.float32, "render_shade_tex: colors")
+        if tuple(col.shape) != (nv, 3) or col.device != dev:
+            raise L.M324Error(f"render_shade_tex: colors must be fp32 [{nv},3] on the clip's device, got {tuple(col.shape)}")
+    vn, normal_stride = None, 0
+    if normals is not None:
+        vn, normal_stride = _render_clip(normals, "render_shade_tex: normals")
+        if tuple(vn.shape) != (T, nv, 3) or vn.device != dev:
+            raise L.M324Error(f"render_shade_tex: normals must be fp32 [{T},{nv},3] on the clip's device, got {tuple(vn.shape)}")
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or any(not 0 <= c <= 255 for c in bg) or not 0.0 <= float(ambient) <= 1.0:
+        raise L.M324Error(f"render_shade_tex: background is three bytes and ambient lies in [0, 1], got {background!r}, {ambient!r}")
+    uvs, th, tw = None, 0, 0
+    if (face_uvs is None) != (mips is None) or (mips is None) != (tex_size is None):
+        raise L.M324Error("render_shade_tex: face_uvs, mips and tex_size go together (a texture needs UVs, UVs need a texture)")
+    if face_uvs is not None:
+        if col is not None:
+            raise L.M324Error("render_shade_tex: a texture and colors are two albedos: give one")
+        uvs = _device_array(face_uvs, torch.float32, "render_shade_tex: face_uvs")
+        if tuple(uvs.shape) != (f.shape[0], 3, 2) or uvs.device != dev:
+            raise L.M324Error(f"render_shade_tex: face_uvs must be fp32 [{f.shape[0]},3,2] on the clip's device, got {tuple(uvs.shape)}")
+        th, tw = (int(s) for s in tex_size)
+        if not _is_device(mips) or mips.dtype != torch.uint8 or not mips.is_contiguous() or mips.device != dev or mips.numel() < texture_plan(th, tw)[1]:
+            raise L.M324Error(f"render_shade_tex: mips must be the contiguous uint8 chain of a {th} x {tw} texture on the clip's device (texture_mips)")
+    So = S // ss
+    if out is None:
+        out = (torch.empty((T, So, So, 3), dtype=torch.uint8, device=dev), torch.empty((T, S, S), dtype=torch.int32, device=dev),
+               torch.empty((T, S, S), dtype=torch.int32, device=dev))
+    rgb, face, depth = out
+    for t, shape, dt, what in ((rgb, (T, So, So, 3), torch.uint8, "rgb"), (face, (T, S, S), torch.int32, "face"), (depth, (T, S, S), torch.int32, "depth")):
+        if not _is_device(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise L.M324Error(f"render_shade_tex: out {what} must be a contiguous {dt} device tensor {shape}")
+    _launch("m324_render_shade_tex", _p(f), f.shape[0], nv, T, S, _p(col), _p(vn), normal_stride, m.ctypes.data, float(ambient),
+            bg[0] | bg[1] << 8 | bg[2] << 16, _p(uvs), _p(mips), th, tw, int(bool(use_mips)), ss, _p(rgb), _p(face), _p(depth), _p(scratch),
+            scratch.numel())
+    _wrote(rgb, face, depth)
+    return rgb, face, depth
+
+
 # ------------------------------------------------------------------------------------------------ perceptual evaluation
 CONV_KPAD = 16                  # M324_CONV_KPAD: the packed weights have 9 Cin rows rounded up to this, zeros behind 9 Cin
 CONV_MAX_CHANNELS = 4096        # M324_CONV_MAX_CHANNELS
