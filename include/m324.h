@@ -693,6 +693,70 @@ int m324_lpips_prepare(const void* src, int mode, int normalize, int images, int
 int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs, long pixels, int channels, float* partial, float* out,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one
+ * topology into a bit grid, the orthographic fill of such a grid, and the popcounts of two grids.  replaces: compute_iou_voxel
+ * of the reference's evaluation/evaluation_pcd.py:612-637 (trimesh's subdivision voxeliser on the CPU; the reference keeps the call
+ * commented out).  The arithmetic below IS the contract: which voxels a triangle marks is decided in integers and marking is a
+ * 32-bit atomic OR, which is idempotent and commutes, so no output depends on arrival order, grid, CU count, queue order or
+ * big_voxels.  Every result is an integer; the quotient of the IoU is formed by the caller.
+ *
+ * Grid: R = resolution, voxels per unit length (pitch 1 / R); H = half, the integer half extent: the grid covers [-H, H)^3 with
+ *   G = 2 H R voxels per axis ("side").  R is a multiple of 16, so G is a multiple of 32; M324_VOXEL_MIN_SIDE <= G <=
+ *   M324_VOXEL_MAX_SIDE.  Voxel (i, j, k) along x, y, z is the CLOSED cube [16 i, 16 i + 16] x [16 j, 16 j + 16] x [16 k, 16 k + 16]
+ *   in sub-voxel units (1/16 voxel).  Occupancy is int32 words [frames, G, G, G / 32]: voxel (i, j, k) of frame t is bit i % 32 of
+ *   word ((t G + k) G + j) (G / 32) + i / 32, read as unsigned.
+ * Sizes: frames >= 1; n_vertices >= 1; n_faces >= 0; frames * n_faces < 2^31 and frames * n_vertices < 2^31.  vertices fp32, frame t
+ *   at vertices + t * stride_t (ELEMENTS), vertex v at + 3 v.  faces int32 [n_faces, 3], shared by every frame; a face with an
+ *   index outside [0, n_vertices) marks nothing (the Python wrappers refuse such faces before any launch).
+ *
+ * Snap, per frame and vertex, for each coordinate c of (x, y, z):
+ *   q_c = rint(clamp((x_c + (float)H) * (float)(16 R), -131072, 131072))
+ *   in uncontracted fp32, with clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v) and rint = round to nearest, ties to even (as in
+ *   m324_render_project).  A vertex with a non-finite coordinate is invalid and every triangle that touches it is skipped.
+ *   outside[t] counts the valid vertices of frame t with some q_c outside [0, 16 G]: geometry the grid does not hold.
+ *
+ * Overlap.  A triangle with integer vertices v_0, v_1, v_2 marks voxel (i, j, k) iff none of 13 axes separates it from the
+ *   voxel's closed cube, all in int64.  c = (16 i + 8, 16 j + 8, 16 k + 8), v'_m = v_m - c; e_0 = v_1 - v_0, e_1 = v_2 - v_1,
+ *   e_2 = v_0 - v_2.
+ *   - the three cube axes a: separated iff min_m v'_ma > 8 or max_m v'_ma < -8;
+ *   - the normal n = e_0 x e_1: separated iff |n . v'_0| > 8 (|n_x| + |n_y| + |n_z|);
+ *   - for each edge e_m and each unit axis u: a = e_m x u, p_l = a . v'_l, r = 8 (|a_x| + |a_y| + |a_z|); separated iff
+ *     min_l p_l > r or max_l p_l < -r.
+ *   Touching counts: a triangle that lies in the plane between two voxel layers marks both.  Degenerate triangles (a segment, a
+ *   point) go through the same 13 tests, which stay exact for them: no special case.  A voxel outside [0, G)^3 is not marked.
+ *   Bounds: |q_c| <= 2^17, edge components <= 2^18, |c_a| < 2^15, so |v'| < 2^18; components of n <= 2^37, 8 (|n_x| + |n_y| + |n_z|)
+ *   < 2^42, and every projection (n . v'_0, a . v'_l) stays below 2^57: this is where G <= 1024 and the clamp come from.
+ * Work distribution (never visible in the result): the voxels that pass the three cube axes, clipped to [0, G - 1] per axis,
+ *   form the triangle's box.  An empty box marks nothing.  A box of at most big_voxels (>= 0) voxels is walked by the lane that
+ *   loaded the triangle; the others are appended to a queue of capacity frames * n_faces (one counter add per wave) and a second
+ *   launch gives each entry a whole workgroup, lanes striding over the box's words.  The bits a walk finds for one word leave in one
+ *   no-return 32-bit atomic OR.  No workgroup waits for another; every loop is bounded by a clipped box or by the queue's capacity.
+ *
+ * m324_voxel_plan: host-only; validates the sizes and stores the scratch bytes of m324_voxelize in *scratch_bytes (may be NULL).
+ * m324_voxelize: ZEROES grid (int32 [frames, G, G, G / 32]) and outside (int32 [frames]) on the stream, then snaps and marks; the
+ *   caller zeroes nothing.  scratch: device memory, 16-byte aligned, m324_voxel_plan bytes for the same sizes.
+ * m324_voxel_fill: the rule usually called orthographic fill.  E_x(i, j, k) is true iff occupied voxels exist at some i1 <= i and
+ *   some i2 >= i in row (j, k) of the frame; E_y and E_z the same along their axes; out = E_x & E_y & E_z, which contains the
+ *   surface.  It is NOT a flood fill: a cup without a lid stays empty (nothing above its inside), but under a lid that covers
+ *   half of it the inside is filled, although it is connected to the outside.  Along x this is bit
+ *   arithmetic within a row of words, along y and z a forward and a backward OR scan per column of words.  out is a second grid
+ *   that does not overlap `grid` (scratch may be NULL), or `grid` itself: then scratch is device memory of the grid's size
+ *   (4 frames G^3 / 32 bytes, 4-byte aligned) and the result is copied back on the stream.
+ * m324_voxel_counts: counts int64 [frames, 3] = (|A|, |B|, |A & B|) of two grids by popcount; a and b 16-byte aligned; frames <=
+ *   65535.  counts is zeroed on the stream; each workgroup reduces its share and issues one 64-bit integer atomic add per
+ *   number: integer addition commutes, so the counts are deterministic.  The caller forms union = |A| + |B| - |A & B| and
+ *   iou = |A & B| / union in fp64, 0.0 when union = 0 (as the reference does).
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_VOXEL_MIN_SIDE 32
+#define M324_VOXEL_MAX_SIDE 1024
+int m324_voxel_plan(int n_vertices, int n_faces, int frames, int resolution, int half, long* scratch_bytes);
+int m324_voxelize(const float* vertices, long stride_t, int n_vertices, const int* faces, int n_faces, int frames, int resolution, int half,
+                  int big_voxels, int* grid, int* outside, void* scratch, long scratch_bytes, void* stream);
+int m324_voxel_fill(const int* grid, int* out, int frames, int side, void* scratch, long scratch_bytes, void* stream);
+int m324_voxel_counts(const int* a, const int* b, int frames, int side, long* counts, void* stream);
+
 /* ==========================================================================================
  * Training-side entry points (backward of the path; reference: torch autograd over the same modules,
  * train.py:150-166).  The backward GEMMs reuse m324_gemm on transposed operands:

@@ -116,6 +116,10 @@ SIGNATURES = {
     "m324_texture_plan": [_I, _I, _P, _P],
     "m324_texture_mips": [_P, _I, _I, _I, _P, _L, _P],
     "m324_render_shade_tex": [_P, _I, _I, _I, _I, _P, _P, _L, _P, _F, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P],
+    "m324_voxel_plan": [_I, _I, _I, _I, _I, _P],
+    "m324_voxelize": [_P, _L, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "m324_voxel_fill": [_P, _P, _I, _I, _P, _L, _P],
+    "m324_voxel_counts": [_P, _P, _I, _I, _P, _P],
     "m324_conv3x3": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "m324_maxpool2x2": [_P, _P, _I, _I, _I, _I, _P],
     "m324_lpips_prepare": [_P, _I, _I, _I, _I, _I, _P, _P],

@@ -1469,6 +1469,103 @@ def render_shade_tex(faces: torch.Tensor, n_vertices: int, frames: int, size: in
     return rgb, face, depth
 
 
+# ------------------------------------------------------------------------------------------------ volumetric IoU
+VOXEL_MIN_SIDE, VOXEL_MAX_SIDE = 32, 1024   # M324_VOXEL_MIN_SIDE, M324_VOXEL_MAX_SIDE
+VOXEL_BIG_VOXELS = 64           # default of big_voxels, measured against 16 / 256 / 1024 (profiles/voxel_iou.md); never in the result
+
+
+def voxel_side(resolution: int, half: int = 2) -> int:
+    """G = 2 * half * resolution, the voxels per axis of the grid over [-half, half)^3, after the refusals of include/m324.h"""
+    if isinstance(resolution, bool) or isinstance(half, bool) or int(resolution) != resolution or int(half) != half:
+        raise L.M324Error(f"voxel grid: resolution and half are integers, got {resolution!r}, {half!r}")
+    resolution, half = int(resolution), int(half)
+    if resolution < 16 or resolution % 16:
+        raise L.M324Error(f"voxel grid: resolution must be a positive multiple of 16, got {resolution}")
+    side = 2 * half * resolution
+    if half < 1 or not VOXEL_MIN_SIDE <= side <= VOXEL_MAX_SIDE:
+        raise L.M324Error(f"voxel grid: the side 2 * half * resolution must be in {VOXEL_MIN_SIDE}..{VOXEL_MAX_SIDE} (half={half} resolution={resolution})")
+    return side
+
+
+def voxel_plan(n_vertices: int, n_faces: int, frames: int, resolution: int, half: int = 2) -> int:
+    """scratch bytes of m324_voxelize for these sizes: m324_voxel_plan, host-only"""
+    return _plan_query("m324_voxel_plan", int(n_vertices), int(n_faces), int(frames), int(resolution), int(half))[1]
+
+
+def _voxel_grid(grid, name: str) -> int:
+    """the side G of a contiguous int32 device grid [T,G,G,G/32]"""
+    _on_device(grid, name)
+    s = tuple(grid.shape)
+    if grid.dtype != torch.int32 or len(s) != 4 or s[0] < 1 or s[1] != s[2] or s[1] != 32 * s[3] or not VOXEL_MIN_SIDE <= s[1] <= VOXEL_MAX_SIDE \
+            or not grid.is_contiguous():
+        raise L.M324Error(f"{name}: expected a contiguous int32 grid [T,G,G,G/32] with G a multiple of 32 in {VOXEL_MIN_SIDE}..{VOXEL_MAX_SIDE}, "
+                          f"got {grid.dtype} {s}")
+    return s[1]
+
+
+def voxelize(vertices: torch.Tensor, faces: torch.Tensor, resolution: int, half: int = 2, big_voxels: Optional[int] = None,
+             scratch: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, faces_checked: bool = False):
+    """Surface occupancy of every frame of a clip (m324_voxelize): vertices fp32 [T,V,3] (a view with contiguous last two axes is
+    used in place), faces int32 [F,3] (F = 0 gives empty grids) -> (grid int32 [T,G,G,G/32], outside int32 [T]) over [-half, half)^3
+    at `resolution` voxels per unit; bit layout and overlap rule in include/m324.h.  outside[t] counts the vertices of frame t the
+    grid does not hold.  big_voxels: boxes larger than this go through the queued pass; None = VOXEL_BIG_VOXELS.  The grid does
+    not depend on it.  out: the grid to write (it is zeroed by the call)."""
+    side = voxel_side(resolution, half)
+    v, stride_t = _render_clip(vertices, "voxelize: vertices")
+    T, nv = v.shape[0], v.shape[1]
+    f = _device_array(faces, torch.int32, "voxelize: faces")
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise L.M324Error(f"voxelize: expected [F,3] int32 faces, got {tuple(f.shape)}")
+    if f.device != v.device:
+        raise L.M324Error("voxelize: vertices and faces live on different devices")
+    nf = f.shape[0]
+    if nf and not faces_checked:
+        _faces_in_range(f, nv, "voxelize")
+    big = VOXEL_BIG_VOXELS if big_voxels is None else int(big_voxels)
+    if not 0 <= big <= 2 ** 31 - 1:
+        raise L.M324Error(f"voxelize: big_voxels must be in 0..2^31-1, got {big_voxels}")
+    need = voxel_plan(nv, nf, T, resolution, half)
+    scratch = _render_scratch(scratch, need, v.device, "voxelize")
+    if out is None:
+        out = torch.empty((T, side, side, side // 32), dtype=torch.int32, device=v.device)
+    elif _voxel_grid(out, "voxelize: out") != side or out.shape[0] != T or out.device != v.device:
+        raise L.M324Error(f"voxelize: out must be an int32 grid [{T},{side},{side},{side // 32}] on the clip's device, got {tuple(out.shape)}")
+    outside = torch.empty((T,), dtype=torch.int32, device=v.device)
+    _launch("m324_voxelize", _p(v), stride_t, nv, _p(f) if nf else None, nf, T, int(resolution), int(half), big, _p(out), _p(outside), _p(scratch),
+            scratch.numel())
+    _wrote(out, outside, scratch)
+    return out, outside
+
+
+def voxel_fill(grid: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Orthographic fill of a grid (m324_voxel_fill): a voxel is set iff occupied voxels lie on both sides of it (or on it) along
+    x, along y and along z.  Returns a new grid; out=grid fills in place (through a temporary of the grid's size), any other
+    out is a second grid of the same shape."""
+    side = _voxel_grid(grid, "voxel_fill")
+    T = grid.shape[0]
+    scratch = None
+    if out is None:
+        out = torch.empty_like(grid)
+    elif out is grid or (_is_device(out) and out.data_ptr() == grid.data_ptr() and out.shape == grid.shape):
+        scratch = torch.empty_like(grid)
+    elif _voxel_grid(out, "voxel_fill: out") != side or out.shape != grid.shape or out.device != grid.device:
+        raise L.M324Error(f"voxel_fill: out must be shaped like grid {tuple(grid.shape)} on its device, got {tuple(out.shape)}")
+    _launch("m324_voxel_fill", _p(grid), _p(out), T, side, _p(scratch), scratch.numel() * 4 if scratch is not None else 0)
+    _wrote(out)
+    return out
+
+
+def voxel_counts(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """int64 [T,3] = (|A|, |B|, |A & B|) per frame of two grids of the same shape (m324_voxel_counts); deterministic"""
+    side = _voxel_grid(a, "voxel_counts: a")
+    if _voxel_grid(b, "voxel_counts: b") != side or a.shape != b.shape or a.device != b.device:
+        raise L.M324Error(f"voxel_counts: two grids of one shape on one device, got {tuple(a.shape)} / {tuple(b.shape)}")
+    counts = torch.empty((a.shape[0], 3), dtype=torch.int64, device=a.device)
+    _launch("m324_voxel_counts", _p(a), _p(b), a.shape[0], side, _p(counts))
+    _wrote(counts)
+    return counts
+
+
 # ------------------------------------------------------------------------------------------------ perceptual evaluation
 CONV_KPAD = 16                  # M324_CONV_KPAD: the packed weights have 9 Cin rows rounded up to this, zeros behind 9 Cin
 CONV_MAX_CHANNELS = 4096        # M324_CONV_MAX_CHANNELS
