@@ -694,6 +694,66 @@ int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Foreground matting (csrc/matting.hip; added at ABI 23 without a bump): the pieces of U2-Net and of the arithmetic the
+ * `rembg` package wraps around it, what motion324_amd/matting.py strings together.  replaces: the per-frame
+ * rembg.remove(frame, session='u2net') loop of the reference's utils/inference_utils.py:segment_foreground_with_u2net
+ * (onnxruntime with a PIL round trip there).  Everything is fp32 unless said otherwise, activations are NHWC ([images, H, W, C],
+ * C contiguous), every pointer is device memory and 16-byte aligned unless said otherwise, images * H * W stays below 2^31.
+ *
+ * m324_conv3x3_ex: m324_conv3x3 generalised.  The input is the channel concatenation of a [images, H, W, Ca] and b [images, H,
+ *   W, Cb] (a's channels first; b = NULL with Cb = 0 for one source), which is never built:
+ *     s[i, y, x, n] = sum over taps t = 3 (dy + 1) + (dx + 1), dy, dx in -1..1, and channels c < Ca + Cb of
+ *                     cat[i, y + dilation dy, x + dilation dx, c] * wp[t (Ca + Cb) + c][n],   a tap outside the image contributes 0,
+ *     out = act(s + bias) + res  with act = max(., 0) when relu = 1 and res [images, H, W, Cout] optional (NULL: nothing added).
+ *   Shape contract: Ca % 4 = Cb % 4 = 0, Ca >= 4, Ca + Cb <= M324_CONV_MAX_CHANNELS; Cout % 4 = 0 in 4..M324_CONV_MAX_CHANNELS;
+ *   dilation in 1..M324_CONV_MAX_DILATION; any H, W, images >= 1.  wp [Kpad, Cout] as for m324_conv3x3 with Cin = Ca + Cb.  A
+ *   convolution with fewer than four outputs (the side outputs: one) is packed with zero columns and a zero bias up to four.
+ *   Arithmetic: that of m324_conv3x3, unchanged -- chains of M324_CONV_RUN consecutive k from 0 on v_mfma_f32_32x32x2_f32, the
+ *   chains added in order, then + bias, the activation, + res (one rounding each).  With dilation 1, b = NULL and res = NULL the
+ *   bits are those of m324_conv3x3 wherever that accepts the shape.  The tile (128 pixels by 128, 64 or 32 channels) is chosen
+ *   from Cout and the pixel count -- m324_conv3x3_ex_tile (host only) returns its width -- and never shows in the bits, nor does
+ *   the image's place in the batch, the grid or a second call.
+ * m324_maxpool2x2_ceil: out[i, y, x, c] = max of in[i, 2y .. min(2y + 1, H - 1), 2x .. min(2x + 1, W - 1), c], out [images,
+ *   ceil(H / 2), ceil(W / 2), C]: MaxPool2d(2, 2, ceil_mode=True).  C % 4 = 0.  Exact.
+ * m324_upsample_bilinear: in [images, H, W, C] -> out [images, Ho, Wo, C], bilinear with align_corners = false; C % 4 = 0, every
+ *   size in 1..M324_MATTE_MAX_SIDE.  Per axis, in fp32 and in this order, nothing contracted:
+ *     scale = (float)in / (float)out;  s = max(((float)o + 0.5f) * scale - 0.5f, 0);  i0 = min((int)s, in - 1);
+ *     i1 = i0 + (i0 < in - 1);  l1 = min(max(s - (float)i0, 0), 1);  l0 = 1 - l1;
+ *   and the value is  y.l0 * (x.l0 * v[y.i0][x.i0] + x.l1 * v[y.i0][x.i1]) + y.l1 * (x.l0 * v[y.i1][x.i0] + x.l1 * v[y.i1][x.i1]).
+ *   Equal sizes copy the input exactly (l1 = 0).
+ * m324_matte_prepare: src uint8 [images, H, W, 3] (dense, any alignment) -> dst fp32 [images, H, W, 4]:
+ *   m = max(largest byte of the frame, 1e-6);  dst_c = (float)(((double)v_c / m - mean_c) / std_c) for c < 3, mean (.485, .456,
+ *   .406), std (.229, .224, .225); dst_3 = 0.  Evaluated in float64 as written and rounded once: the bits numpy gets.
+ *   frame_max: int [images], written (the per-frame maximum, an integer reduction); partial: scratch of images *
+ *   M324_MATTE_CHUNKS ints.  The reduction has two levels -- a frame is cut into min(M324_MATTE_CHUNKS, ceil(n /
+ *   M324_MATTE_CHUNK_ITEMS)) equal runs, a workgroup per run, a second kernel over a frame's runs -- so that a few frames fill the chip.
+ * m324_matte_fuse: the fused side-output head.  sides, side_h, side_w: HOST arrays of M324_MATTE_SIDES device pointers and sizes,
+ *   map k fp32 [images, side_h[k], side_w[k], side_stride] of which channel 0 is read (4-byte aligned); outconv: HOST array of
+ *   M324_MATTE_SIDES weights and the bias.  Per output pixel of [images, Ho, Wo]: u_k = map k sampled as m324_upsample_bilinear
+ *   samples it (side_h[k] <= Ho, side_w[k] <= Wo), d0 = ((((((0 + w_0 u_0) + w_1 u_1) + ...) + w_5 u_5) + bias, nothing contracted;
+ *   prob = 1 / (1 + expf(-d0)); logit (optional) receives d0.
+ * m324_matte_quantise: p fp32 [images, pixels] -> q uint8: per frame mi = min p, ma = max p (exact in any order; written to
+ *   minmax fp32 [images, 2]), q = (uint8)(((p - mi) / (ma - mi)) * 255) in fp32 as written, truncated.  A frame with ma = mi
+ *   (numpy: NaN) gives q = 0.  partial: scratch of images * M324_MATTE_CHUNKS * 2 floats, the two levels of m324_matte_prepare.
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.  No
+ * atomics anywhere: every result is a fixed sequence of operations.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_CONV_MAX_DILATION 64
+#define M324_MATTE_SIDES 6
+#define M324_MATTE_MAX_SIDE 16384
+#define M324_MATTE_CHUNKS 64
+#define M324_MATTE_CHUNK_ITEMS 4096
+int m324_conv3x3_ex(const float* a, int Ca, const float* b, int Cb, const float* wp, const float* bias, const float* res, float* out,
+                    int images, int H, int W, int Cout, int dilation, int relu, void* stream);
+int m324_conv3x3_ex_tile(int images, int H, int W, int Cout);
+int m324_maxpool2x2_ceil(const float* in, float* out, int images, int H, int W, int C, void* stream);
+int m324_upsample_bilinear(const float* in, float* out, int images, int H, int W, int Ho, int Wo, int C, void* stream);
+int m324_matte_prepare(const unsigned char* src, int images, int H, int W, int* partial, int* frame_max, float* dst, void* stream);
+int m324_matte_fuse(const float* const* sides, const int* side_h, const int* side_w, int side_stride, const float* outconv, int images,
+                    int Ho, int Wo, float* prob, float* logit, void* stream);
+int m324_matte_quantise(const float* p, int images, long pixels, float* partial, float* minmax, unsigned char* q, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one
  * topology into a bit grid, the orthographic fill of such a grid, and the popcounts of two grids.  replaces: compute_iou_voxel
  * of the reference's evaluation/evaluation_pcd.py:612-637 (trimesh's subdivision voxeliser on the CPU; the reference keeps the call

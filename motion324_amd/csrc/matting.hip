@@ -1,0 +1,511 @@
+// Foreground matting (U2-Net): the generalised 3 x 3 convolution, the ceil-mode pool, the bilinear upsample, the input
+// normalisation, the fused side-output head and the quantisation of the matte.  The contract of every entry point is in
+// include/m324.h; what is here is how.
+//
+// m324_conv3x3_ex is the implicit GEMM of csrc/perceptual.hip (read its header first) with three more degrees of freedom: the
+// taps lie `dilation` pixels apart, the K axis runs over the channels of TWO tensors (a piece of four channels comes from `a`
+// when c < Ca and from `b` otherwise; Ca % 4 = 0, so no piece straddles them and the concatenation never exists in memory), and
+// the epilogue can add a residual behind the activation.  The sum is the same: v_mfma_f32_32x32x2_f32 over 16 k per step,
+// M324_CONV_RUN consecutive k per chain, the chains added in order.  What varies with the layer is the tile only: 128 pixels by
+// BN = 128, 64 or 32 output channels.  BN = 128 and 64 split the tile over 2 x 2 waves as m324_conv3x3 does; BN = 32 stacks the
+// four waves along the pixels, one 32 x 32 accumulator each, so that a 16- or 32-channel layer wastes at most the columns
+// past Cout of ONE 32-wide tile (the fp32 MFMA whose chain the contract states is 32 wide).  A 256 x 64 tile of four 64 x 64
+// waves, which has the MFMA-to-LDS-read ratio of the 128-wide tile, was measured for the 64-channel layers and lost 4 to 10 %
+// against 128 x 64 (184 VGPRs and 45 KB of LDS: fewer waves per CU); profiles/matting.md has the numbers.  An output's bits do not
+// depend on the tile: every tile runs the same chain for it.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int BM = 128;
+constexpr int BK = M324_CONV_KPAD;
+constexpr int RUN_STEPS = M324_CONV_RUN / BK;
+constexpr int FILL_WORKGROUPS = 512;    // below this many 128-wide tiles the chip is not full and the narrower tile is taken
+
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+template <int BN, int WN>                      // WN waves along the channels, 4 / WN along the pixels
+__global__ __launch_bounds__(THREADS) void conv3x3_ex_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ wp,
+                                                             const float* __restrict__ bias, const float* __restrict__ res, float* __restrict__ out,
+                                                             long M, int H, int W, int Ca, int Cb, int Cout, int K, int n_tiles, int dil, int relu) {
+    constexpr int NP = BM / 64;                     // pixels this thread fetches per step
+    constexpr int LDA = BM + 4;                     // 4 * LDA = 16 mod 64: the four pieces of 16 pixels land in 64 different banks
+    constexpr int TM = BM / (32 * (4 / WN));        // 32-row accumulator tiles per wave
+    constexpr int TN = BN / (32 * WN);              // 32-column accumulator tiles per wave
+    constexpr int LDB = BN % 64 == 0 ? BN + 32 : BN;        // LDB = 32 mod 64: the two k rows of a B operand read disjoint banks
+    constexpr int BPIECES = BK * BN / 4;            // 16-byte pieces of the weight tile
+    constexpr int BQ = (BPIECES + THREADS - 1) / THREADS;
+    __shared__ float As[2][BK * LDA];
+    __shared__ float Bs[2][BK * LDB];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long m0 = (long)(blockIdx.x / n_tiles) * BM;
+    const int n0 = (blockIdx.x % n_tiles) * BN;
+    const int C = Ca + Cb;
+
+    // the NP pixels this thread fetches, and the piece (four channels) of the step it fetches for all of them
+    const int kq = tid & 3;
+    long pix[NP];
+    int px[NP], py[NP];
+    bool pv[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const long p = m0 + (tid >> 2) + 64 * i;
+        pv[i] = p < M;
+        pix[i] = pv[i] ? p : 0;
+        px[i] = (int)(pix[i] % W);
+        py[i] = (int)((pix[i] / W) % H);
+    }
+    int bk[BQ], bn[BQ];
+    bool bv[BQ];
+#pragma unroll
+    for (int i = 0; i < BQ; ++i) {
+        const int idx = tid + THREADS * i;
+        bv[i] = idx < BPIECES;
+        bk[i] = bv[i] ? idx / (BN / 4) : 0;
+        bn[i] = bv[i] ? (idx % (BN / 4)) * 4 : 0;
+        bv[i] = bv[i] && n0 + bn[i] < Cout;
+    }
+
+    float4 ra[NP], rb[BQ];
+    auto fetch = [&](int k0) {
+        const int k = k0 + kq * 4;
+        const int tap = k / C, c = k - tap * C;
+        const int dy = (tap / 3 - 1) * dil, dx = (tap - (tap / 3) * 3 - 1) * dil;
+        const bool first = c < Ca;
+        const float* src = first ? a : b;
+        const int cs = first ? Ca : Cb, cc = first ? c : c - Ca;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const bool ok = pv[i] && k < K && (unsigned)(py[i] + dy) < (unsigned)H && (unsigned)(px[i] + dx) < (unsigned)W;
+            ra[i] = ok ? *reinterpret_cast<const float4*>(src + (pix[i] + (long)dy * W + dx) * cs + cc) : zero4();
+        }
+#pragma unroll
+        for (int i = 0; i < BQ; ++i)
+            rb[i] = bv[i] ? *reinterpret_cast<const float4*>(wp + (long)(k0 + bk[i]) * Cout + n0 + bn[i]) : zero4();
+    };
+    auto stage = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            float* s = &As[buf][(kq * 4) * LDA + (tid >> 2) + 64 * i];
+            s[0] = ra[i].x; s[LDA] = ra[i].y; s[2 * LDA] = ra[i].z; s[3 * LDA] = ra[i].w;
+        }
+#pragma unroll
+        for (int i = 0; i < BQ; ++i)
+            if (tid + THREADS * i < BPIECES) *reinterpret_cast<float4*>(&Bs[buf][bk[i] * LDB + bn[i]]) = rb[i];
+    };
+
+    f32x16 acc[TM][TN], tot[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[i][j][r] = 0.f;
+
+    const int wm = (wave / WN) * (32 * TM), wn = (wave % WN) * (32 * TN);
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int steps = (K + BK - 1) / BK;
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (int s = 0; s < steps; ++s) {
+        const int buf = s & 1;
+        if (s + 1 < steps) fetch((s + 1) * BK);
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk) {
+            const int k = 2 * kk + lh;              // lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31]
+            float av[TM], bw[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) av[i] = As[buf][k * LDA + wm + 32 * i + l31];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) bw[j] = Bs[buf][k * LDB + wn + 32 * j + l31];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bw[j], acc[i][j], 0, 0, 0);
+        }
+        if ((s + 1) % RUN_STEPS == 0) {             // a run of M324_CONV_RUN products ends: second level of the sum
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        tot[i][j][r] += acc[i][j][r];
+                        acc[i][j][r] = 0.f;
+                    }
+        }
+        if (s + 1 < steps) stage(buf ^ 1);          // last read in step s - 1, behind that step's barrier
+        __syncthreads();
+    }
+
+    // C/D of the 32 x 32 MFMA: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = n0 + wn + 32 * j + l31;
+        if (n >= Cout) continue;
+        const float bv0 = bias[n];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long p = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (p < M) {
+                    float v = (tot[i][j][r] + acc[i][j][r]) + bv0;
+                    if (relu) v = v > 0.f ? v : 0.f;
+                    if (res) v = v + res[p * Cout + n];
+                    out[p * Cout + n] = v;
+                }
+            }
+    }
+}
+
+__device__ __forceinline__ float4 max4(float4 a, float4 b) {
+    return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+}
+
+__global__ __launch_bounds__(THREADS) void maxpool2x2_ceil_kernel(const float4* __restrict__ in, float4* __restrict__ out, long total, int H, int W,
+                                                                  int Ho, int Wo, int C4) {
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % C4);
+    long r = i / C4;
+    const int x = (int)(r % Wo);
+    r /= Wo;
+    const int y = (int)(r % Ho);
+    const long img = r / Ho;
+    const bool right = 2 * x + 1 < W, below = 2 * y + 1 < H;      // the window is cut at the edge
+    const float4* s = in + ((img * H + 2 * y) * W + 2 * x) * C4 + c;
+    float4 v = s[0];
+    if (right) v = max4(v, s[C4]);
+    if (below) v = max4(v, s[(long)W * C4]);
+    if (right && below) v = max4(v, s[(long)W * C4 + C4]);
+    out[i] = v;
+}
+
+// one axis of the bilinear resize (align_corners = false): the two source samples of output o and their weights
+struct Lerp {
+    int i0, i1;
+    float l0, l1;
+};
+
+__device__ __forceinline__ Lerp lerp_of(int o, int in, int out) {
+#pragma clang fp contract(off)
+    const float scale = (float)in / (float)out;
+    float s = ((float)o + 0.5f) * scale - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    Lerp r;
+    r.i0 = (int)s;
+    r.i0 = r.i0 > in - 1 ? in - 1 : r.i0;
+    r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
+    r.l1 = fminf(fmaxf(s - (float)r.i0, 0.f), 1.f);
+    r.l0 = 1.0f - r.l1;
+    return r;
+}
+
+__device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, const Lerp& y, const Lerp& x) {
+#pragma clang fp contract(off)
+    return y.l0 * (x.l0 * v00 + x.l1 * v01) + y.l1 * (x.l0 * v10 + x.l1 * v11);
+}
+
+__global__ __launch_bounds__(THREADS) void upsample_bilinear_kernel(const float4* __restrict__ in, float4* __restrict__ out, long total, int H, int W,
+                                                                    int Ho, int Wo, int C4) {
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % C4);
+    long r = i / C4;
+    const int x = (int)(r % Wo);
+    r /= Wo;
+    const int y = (int)(r % Ho);
+    const long img = r / Ho;
+    const Lerp ly = lerp_of(y, H, Ho), lx = lerp_of(x, W, Wo);
+    const float4* s = in + img * H * W * C4 + c;
+    const float4 v00 = s[((long)ly.i0 * W + lx.i0) * C4], v01 = s[((long)ly.i0 * W + lx.i1) * C4];
+    const float4 v10 = s[((long)ly.i1 * W + lx.i0) * C4], v11 = s[((long)ly.i1 * W + lx.i1) * C4];
+    out[i] = make_float4(bilerp(v00.x, v01.x, v10.x, v11.x, ly, lx), bilerp(v00.y, v01.y, v10.y, v11.y, ly, lx),
+                         bilerp(v00.z, v01.z, v10.z, v11.z, ly, lx), bilerp(v00.w, v01.w, v10.w, v11.w, ly, lx));
+}
+
+// The per-frame reductions have two levels so that a clip of a few frames still fills the chip: a frame is cut into `chunks` equal
+// runs, a workgroup reduces one run, and a second kernel reduces a frame's runs.  Maxima and minima are exact in any order.
+int chunks_of(long n) {
+    const long c = (n + M324_MATTE_CHUNK_ITEMS - 1) / M324_MATTE_CHUNK_ITEMS;
+    return (int)(c < M324_MATTE_CHUNKS ? c : M324_MATTE_CHUNKS);
+}
+
+// the largest byte of every run of every frame
+__global__ __launch_bounds__(THREADS) void frame_bytemax_kernel(const unsigned char* __restrict__ src, long bytes, int chunks, int* __restrict__ partial) {
+    __shared__ int red[THREADS];
+    const long frame = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const long per = (bytes + chunks - 1) / chunks;
+    const long p0 = chunk * per, p1 = p0 + per < bytes ? p0 + per : bytes;
+    const unsigned char* s = src + frame * bytes;
+    int m = 0;
+    for (long i = p0 + threadIdx.x; i < p1; i += THREADS) m = max(m, (int)s[i]);
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] = max(red[threadIdx.x], red[threadIdx.x + off]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(64) void frame_bytemax_finish_kernel(const int* __restrict__ partial, int images, int chunks, int* __restrict__ frame_max) {
+    const int img = blockIdx.x * 64 + threadIdx.x;
+    if (img >= images) return;
+    int m = 0;
+    for (int i = 0; i < chunks; ++i) m = max(m, partial[(long)img * chunks + i]);
+    frame_max[img] = m;
+}
+
+// x_c = (v_c / m - mean_c) / std_c in float64, rounded once to fp32: what numpy computes for the same bytes
+__global__ __launch_bounds__(THREADS) void matte_prepare_kernel(const unsigned char* __restrict__ src, const int* __restrict__ frame_max, long total,
+                                                                long HW, float4* __restrict__ dst) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int fm = frame_max[i / HW];
+    const double m = fm > 0 ? (double)fm : 1e-6;
+    const unsigned char* s = src + 3 * i;
+    const double x0 = ((double)s[0] / m - 0.485) / 0.229, x1 = ((double)s[1] / m - 0.456) / 0.224, x2 = ((double)s[2] / m - 0.406) / 0.225;
+    dst[i] = make_float4((float)x0, (float)x1, (float)x2, 0.f);
+}
+
+struct FuseArgs {
+    const float* side[M324_MATTE_SIDES];
+    int h[M324_MATTE_SIDES], w[M324_MATTE_SIDES];
+    float weight[M324_MATTE_SIDES];
+    float bias;
+};
+
+__global__ __launch_bounds__(THREADS) void matte_fuse_kernel(FuseArgs fa, int stride, long total, int Ho, int Wo, float* __restrict__ prob,
+                                                             float* __restrict__ logit) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % Wo);
+    const long r = i / Wo;
+    const int y = (int)(r % Ho);
+    const long img = r / Ho;
+    float d0 = 0.f;
+#pragma unroll
+    for (int k = 0; k < M324_MATTE_SIDES; ++k) {
+        const int h = fa.h[k], w = fa.w[k];
+        const Lerp ly = lerp_of(y, h, Ho), lx = lerp_of(x, w, Wo);
+        const float* s = fa.side[k] + img * h * w * stride;
+        const float v = bilerp(s[((long)ly.i0 * w + lx.i0) * stride], s[((long)ly.i0 * w + lx.i1) * stride],
+                               s[((long)ly.i1 * w + lx.i0) * stride], s[((long)ly.i1 * w + lx.i1) * stride], ly, lx);
+        d0 = d0 + fa.weight[k] * v;
+    }
+    d0 = d0 + fa.bias;
+    if (logit) logit[i] = d0;
+    prob[i] = 1.0f / (1.0f + expf(-d0));
+}
+
+// the smallest and the largest value of every run of every frame
+__global__ __launch_bounds__(THREADS) void frame_minmax_kernel(const float* __restrict__ p, long pixels, int chunks, float* __restrict__ partial) {
+    __shared__ float lo[THREADS], hi[THREADS];
+    const long frame = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const long per = (pixels + chunks - 1) / chunks;
+    const long p0 = chunk * per, p1 = p0 + per < pixels ? p0 + per : pixels;
+    const float* s = p + frame * pixels;
+    float a = INFINITY, b = -INFINITY;
+    for (long i = p0 + threadIdx.x; i < p1; i += THREADS) {
+        const float v = s[i];
+        a = fminf(a, v);
+        b = fmaxf(b, v);
+    }
+    lo[threadIdx.x] = a;
+    hi[threadIdx.x] = b;
+    __syncthreads();
+    for (int off = THREADS / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            lo[threadIdx.x] = fminf(lo[threadIdx.x], lo[threadIdx.x + off]);
+            hi[threadIdx.x] = fmaxf(hi[threadIdx.x], hi[threadIdx.x + off]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[2L * blockIdx.x] = lo[0];
+        partial[2L * blockIdx.x + 1] = hi[0];
+    }
+}
+
+__global__ __launch_bounds__(64) void frame_minmax_finish_kernel(const float* __restrict__ partial, int images, int chunks, float* __restrict__ minmax) {
+    const int img = blockIdx.x * 64 + threadIdx.x;
+    if (img >= images) return;
+    float a = INFINITY, b = -INFINITY;
+    for (int i = 0; i < chunks; ++i) {
+        a = fminf(a, partial[2 * ((long)img * chunks + i)]);
+        b = fmaxf(b, partial[2 * ((long)img * chunks + i) + 1]);
+    }
+    minmax[2 * img] = a;
+    minmax[2 * img + 1] = b;
+}
+
+__global__ __launch_bounds__(THREADS) void matte_quantise_kernel(const float* __restrict__ p, const float* __restrict__ minmax, long total, long pixels,
+                                                                 unsigned char* __restrict__ q) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const long img = i / pixels;
+    const float mi = minmax[2 * img], ma = minmax[2 * img + 1];
+    float v = 0.f;
+    if (ma > mi) v = ((p[i] - mi) / (ma - mi)) * 255.0f;
+    v = v >= 0.f ? v : 0.f;                         // also a NaN input
+    q[i] = (unsigned char)(v > 255.f ? 255.f : v);  // truncation, as numpy's astype(uint8)
+}
+
+// The tile's width from Cout and the pixel count M: the widest one that divides Cout while it still fills the chip
+int tile_of(long M, int Cout) {
+    if (Cout % 128 == 0 && (M + BM - 1) / BM * (Cout / 128) >= FILL_WORKGROUPS) return 128;
+    return Cout > 32 ? 64 : 32;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+unsigned blocks_of(long total) { return (unsigned)((total + THREADS - 1) / THREADS); }
+
+}  // namespace
+
+extern "C" int m324_conv3x3_ex(const float* a, int Ca, const float* b, int Cb, const float* wp, const float* bias, const float* res, float* out,
+                               int images, int H, int W, int Cout, int dilation, int relu, void* stream) {
+    M324_REQUIRE(a && wp && bias && out, "m324_conv3x3_ex: null a, wp, bias or out");
+    M324_REQUIRE(images >= 1 && H >= 1 && W >= 1, "m324_conv3x3_ex: images, H and W must be at least 1, got %d, %d, %d", images, H, W);
+    M324_REQUIRE(Ca >= 4 && Ca % 4 == 0, "m324_conv3x3_ex: Ca must be a positive multiple of 4, got %d", Ca);
+    M324_REQUIRE((b == nullptr && Cb == 0) || (b != nullptr && Cb >= 4 && Cb % 4 == 0),
+                 "m324_conv3x3_ex: Cb must be 0 with b null, or a positive multiple of 4 with b given, got %d", Cb);
+    M324_REQUIRE(Cout >= 4 && Cout % 4 == 0, "m324_conv3x3_ex: Cout must be a positive multiple of 4, got %d", Cout);
+    M324_REQUIRE(Ca <= M324_CONV_MAX_CHANNELS && Cb <= M324_CONV_MAX_CHANNELS && Ca + Cb <= M324_CONV_MAX_CHANNELS && Cout <= M324_CONV_MAX_CHANNELS,
+                 "m324_conv3x3_ex: at most %d channels (Ca + Cb, and Cout), got Ca %d, Cb %d, Cout %d", M324_CONV_MAX_CHANNELS, Ca, Cb, Cout);
+    const long M = (long)images * H * W;
+    M324_REQUIRE(M <= 0x7fffffffL && (long)H * W <= 0x7fffffffL, "m324_conv3x3_ex: images * H * W must stay below 2^31, got %ld", M);
+    M324_REQUIRE(dilation >= 1 && dilation <= M324_CONV_MAX_DILATION, "m324_conv3x3_ex: dilation must be in 1..%d, got %d", M324_CONV_MAX_DILATION,
+                 dilation);
+    M324_REQUIRE(aligned16(a) && aligned16(b) && aligned16(wp) && aligned16(out), "m324_conv3x3_ex: a, b, wp and out must be 16-byte aligned");
+    M324_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)res & 3) == 0, "m324_conv3x3_ex: bias and res must be 4-byte aligned");
+    M324_REQUIRE(relu == 0 || relu == 1, "m324_conv3x3_ex: relu is 0 or 1, got %d", relu);
+    const int K = 9 * (Ca + Cb);
+    const int width = tile_of(M, Cout);
+    const int n_tiles = (Cout + width - 1) / width;
+    const dim3 grid((unsigned)((M + BM - 1) / BM * n_tiles));
+    hipStream_t st = (hipStream_t)stream;
+#define M324_CONV_EX_LAUNCH(BN_, WN_)                                                                                                    \
+    hipLaunchKernelGGL((conv3x3_ex_kernel<BN_, WN_>), grid, dim3(THREADS), 0, st, a, b, wp, bias, res, out, M, H, W, Ca, Cb, Cout, K, n_tiles, \
+                       dilation, relu)
+    if (width == 128)
+        M324_CONV_EX_LAUNCH(128, 2);
+    else if (width == 64)
+        M324_CONV_EX_LAUNCH(64, 2);
+    else
+        M324_CONV_EX_LAUNCH(32, 1);
+#undef M324_CONV_EX_LAUNCH
+    M324_CHECK_LAUNCH("m324_conv3x3_ex");
+    return M324_OK;
+}
+
+extern "C" int m324_conv3x3_ex_tile(int images, int H, int W, int Cout) {
+    if (images < 1 || H < 1 || W < 1 || Cout < 4 || Cout % 4) return M324_ERR_INVALID;
+    return tile_of((long)images * H * W, Cout);
+}
+
+extern "C" int m324_maxpool2x2_ceil(const float* in, float* out, int images, int H, int W, int C, void* stream) {
+    M324_REQUIRE(in && out, "m324_maxpool2x2_ceil: null in or out");
+    M324_REQUIRE(images >= 1 && H >= 1 && W >= 1, "m324_maxpool2x2_ceil: images, H and W must be at least 1, got %d, %d, %d", images, H, W);
+    M324_REQUIRE(C >= 4 && C % 4 == 0 && C <= M324_CONV_MAX_CHANNELS, "m324_maxpool2x2_ceil: C must be a multiple of 4 in 4..%d, got %d",
+                 M324_CONV_MAX_CHANNELS, C);
+    M324_REQUIRE((long)images * H * W <= 0x7fffffffL, "m324_maxpool2x2_ceil: images * H * W must stay below 2^31");
+    M324_REQUIRE(aligned16(in) && aligned16(out), "m324_maxpool2x2_ceil: in and out must be 16-byte aligned");
+    const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+    const long total = (long)images * Ho * Wo * (C / 4);
+    hipLaunchKernelGGL(maxpool2x2_ceil_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, (const float4*)in, (float4*)out, total,
+                       H, W, Ho, Wo, C / 4);
+    M324_CHECK_LAUNCH("m324_maxpool2x2_ceil");
+    return M324_OK;
+}
+
+extern "C" int m324_upsample_bilinear(const float* in, float* out, int images, int H, int W, int Ho, int Wo, int C, void* stream) {
+    M324_REQUIRE(in && out, "m324_upsample_bilinear: null in or out");
+    M324_REQUIRE(images >= 1 && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "m324_upsample_bilinear: images and all sizes must be at least 1, got %d, %d x %d -> %d x %d",
+                 images, H, W, Ho, Wo);
+    M324_REQUIRE(H <= M324_MATTE_MAX_SIDE && W <= M324_MATTE_MAX_SIDE && Ho <= M324_MATTE_MAX_SIDE && Wo <= M324_MATTE_MAX_SIDE,
+                 "m324_upsample_bilinear: sizes up to %d, got %d x %d -> %d x %d", M324_MATTE_MAX_SIDE, H, W, Ho, Wo);
+    M324_REQUIRE(C >= 4 && C % 4 == 0 && C <= M324_CONV_MAX_CHANNELS, "m324_upsample_bilinear: C must be a multiple of 4 in 4..%d, got %d",
+                 M324_CONV_MAX_CHANNELS, C);
+    M324_REQUIRE((long)images * H * W <= 0x7fffffffL && (long)images * Ho * Wo <= 0x7fffffffL,
+                 "m324_upsample_bilinear: images * H * W and images * Ho * Wo must stay below 2^31");
+    M324_REQUIRE(aligned16(in) && aligned16(out), "m324_upsample_bilinear: in and out must be 16-byte aligned");
+    const long total = (long)images * Ho * Wo * (C / 4);
+    hipLaunchKernelGGL(upsample_bilinear_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, (const float4*)in, (float4*)out, total,
+                       H, W, Ho, Wo, C / 4);
+    M324_CHECK_LAUNCH("m324_upsample_bilinear");
+    return M324_OK;
+}
+
+extern "C" int m324_matte_prepare(const unsigned char* src, int images, int H, int W, int* partial, int* frame_max, float* dst, void* stream) {
+    M324_REQUIRE(src && partial && frame_max && dst, "m324_matte_prepare: null src, partial, frame_max or dst");
+    M324_REQUIRE(images >= 1 && H >= 1 && W >= 1 && (long)images * H * W <= 0x7fffffffL,
+                 "m324_matte_prepare: images, H, W >= 1 and images * H * W below 2^31, got %d, %d, %d", images, H, W);
+    M324_REQUIRE(aligned16(dst) && (((uintptr_t)frame_max | (uintptr_t)partial) & 3) == 0,
+                 "m324_matte_prepare: dst must be 16-byte, partial and frame_max 4-byte aligned");
+    const long HW = (long)H * W, total = images * HW;
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = chunks_of(3 * HW);
+    hipLaunchKernelGGL(frame_bytemax_kernel, dim3((unsigned)((long)images * chunks)), dim3(THREADS), 0, st, src, 3 * HW, chunks, partial);
+    M324_CHECK_LAUNCH("m324_matte_prepare");
+    hipLaunchKernelGGL(frame_bytemax_finish_kernel, dim3((unsigned)((images + 63) / 64)), dim3(64), 0, st, (const int*)partial, images, chunks, frame_max);
+    M324_CHECK_LAUNCH("m324_matte_prepare");
+    hipLaunchKernelGGL(matte_prepare_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, st, src, (const int*)frame_max, total, HW, (float4*)dst);
+    M324_CHECK_LAUNCH("m324_matte_prepare");
+    return M324_OK;
+}
+
+extern "C" int m324_matte_fuse(const float* const* sides, const int* side_h, const int* side_w, int side_stride, const float* outconv, int images,
+                               int Ho, int Wo, float* prob, float* logit, void* stream) {
+    M324_REQUIRE(sides && side_h && side_w && outconv && prob, "m324_matte_fuse: null sides, side_h, side_w, outconv or prob");
+    M324_REQUIRE(images >= 1 && Ho >= 1 && Wo >= 1 && Ho <= M324_MATTE_MAX_SIDE && Wo <= M324_MATTE_MAX_SIDE && (long)images * Ho * Wo <= 0x7fffffffL,
+                 "m324_matte_fuse: images >= 1, Ho and Wo in 1..%d, images * Ho * Wo below 2^31, got %d, %d, %d", M324_MATTE_MAX_SIDE, images, Ho, Wo);
+    M324_REQUIRE(side_stride >= 1 && side_stride <= M324_CONV_MAX_CHANNELS, "m324_matte_fuse: side_stride must be in 1..%d, got %d",
+                 M324_CONV_MAX_CHANNELS, side_stride);
+    M324_REQUIRE((((uintptr_t)prob | (uintptr_t)logit) & 3) == 0, "m324_matte_fuse: prob and logit must be 4-byte aligned");
+    FuseArgs fa;
+    for (int k = 0; k < M324_MATTE_SIDES; ++k) {
+        M324_REQUIRE(sides[k] && ((uintptr_t)sides[k] & 3) == 0, "m324_matte_fuse: side map %d is null or not 4-byte aligned", k);
+        M324_REQUIRE(side_h[k] >= 1 && side_w[k] >= 1 && side_h[k] <= Ho && side_w[k] <= Wo,
+                     "m324_matte_fuse: side map %d must be between 1 x 1 and the output's %d x %d, got %d x %d", k, Ho, Wo, side_h[k], side_w[k]);
+        M324_REQUIRE(isfinite(outconv[k]), "m324_matte_fuse: outconv weight %d is not finite", k);
+        fa.side[k] = sides[k];
+        fa.h[k] = side_h[k];
+        fa.w[k] = side_w[k];
+        fa.weight[k] = outconv[k];
+    }
+    M324_REQUIRE(isfinite(outconv[M324_MATTE_SIDES]), "m324_matte_fuse: the outconv bias is not finite");
+    fa.bias = outconv[M324_MATTE_SIDES];
+    const long total = (long)images * Ho * Wo;
+    hipLaunchKernelGGL(matte_fuse_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, fa, side_stride, total, Ho, Wo, prob, logit);
+    M324_CHECK_LAUNCH("m324_matte_fuse");
+    return M324_OK;
+}
+
+extern "C" int m324_matte_quantise(const float* p, int images, long pixels, float* partial, float* minmax, unsigned char* q, void* stream) {
+    M324_REQUIRE(p && partial && minmax && q, "m324_matte_quantise: null p, partial, minmax or q");
+    M324_REQUIRE(images >= 1 && pixels >= 1 && (long)images * pixels <= 0x7fffffffL && pixels <= 0x7fffffffL,
+                 "m324_matte_quantise: images, pixels >= 1 and images * pixels below 2^31, got %d, %ld", images, pixels);
+    M324_REQUIRE((((uintptr_t)p | (uintptr_t)partial | (uintptr_t)minmax) & 3) == 0, "m324_matte_quantise: p, partial and minmax must be 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = chunks_of(pixels);
+    hipLaunchKernelGGL(frame_minmax_kernel, dim3((unsigned)((long)images * chunks)), dim3(THREADS), 0, st, p, pixels, chunks, partial);
+    M324_CHECK_LAUNCH("m324_matte_quantise");
+    hipLaunchKernelGGL(frame_minmax_finish_kernel, dim3((unsigned)((images + 63) / 64)), dim3(64), 0, st, (const float*)partial, images, chunks, minmax);
+    M324_CHECK_LAUNCH("m324_matte_quantise");
+    const long total = images * pixels;
+    hipLaunchKernelGGL(matte_quantise_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, st, p, (const float*)minmax, total, pixels, q);
+    M324_CHECK_LAUNCH("m324_matte_quantise");
+    return M324_OK;
+}

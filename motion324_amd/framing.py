@@ -2,8 +2,9 @@
 
 replaces: utils/rmbg_for_black_bg.py (compute_mask_bbox, merge_bbox, crop_and_center_to_512 and the masking inside
 remove_background / process_images_in_folder; a PIL loop per frame that scripts/4D_from_video.sh runs before inference) and the
-soft masking of utils/inference_utils.py:segment_foreground_with_u2net.  The matting network itself is not part of this: the
-input is RGBA frames, or RGB plus alpha, from whichever tool made the matte.
+soft masking of utils/inference_utils.py:segment_foreground_with_u2net.  The matting network is not part of this module: the
+input is RGBA frames, or RGB plus alpha -- from motion324_amd.matting (matte_video(...).alpha, U2-Net on the device) or from
+whichever other tool made the matte.
 
 What runs where.  The kernels of csrc/framing.hip do everything that touches a pixel: masking, per-frame boxes, the first pass
 (crop + masking + resampling into a uint8 intermediate; the horizontal one, see pass_order) and the second pass (resampling +

@@ -124,6 +124,13 @@ SIGNATURES = {
     "m324_maxpool2x2": [_P, _P, _I, _I, _I, _I, _P],
     "m324_lpips_prepare": [_P, _I, _I, _I, _I, _I, _P, _P],
     "m324_lpips_layer": [_P, _P, _P, _I, _L, _I, _P, _P, _P],
+    "m324_conv3x3_ex": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "m324_conv3x3_ex_tile": [_I, _I, _I, _I],
+    "m324_maxpool2x2_ceil": [_P, _P, _I, _I, _I, _I, _P],
+    "m324_upsample_bilinear": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "m324_matte_prepare": [_P, _I, _I, _I, _P, _P, _P, _P],
+    "m324_matte_fuse": [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "m324_matte_quantise": [_P, _I, _L, _P, _P, _P, _P],
     "m324_transpose": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_colsum": [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "m324_colsum_multi": [C.POINTER(ColsumItem), _I, _P],

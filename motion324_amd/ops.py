@@ -1665,6 +1665,141 @@ def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: Option
     return out
 
 
+# ------------------------------------------------------------------------------------------------ foreground matting
+CONV_MAX_DILATION = 64          # M324_CONV_MAX_DILATION
+MATTE_SIDES = 6                 # M324_MATTE_SIDES
+MATTE_MAX_SIDE = 16384          # M324_MATTE_MAX_SIDE
+MATTE_CHUNKS = 64               # M324_MATTE_CHUNKS: runs per frame of the two-level per-frame reductions
+
+
+def conv3x3_ex_tile(images: int, H: int, W: int, cout: int) -> int:
+    """output channels per workgroup tile (128, 64 or 32) m324_conv3x3_ex takes for this shape: host-only, never in the bits"""
+    n = int(L.load().m324_conv3x3_ex_tile(int(images), int(H), int(W), int(cout)))
+    L.check(0 if n > 0 else n, "m324_conv3x3_ex_tile")
+    return n
+
+
+def conv3x3_ex(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, b: Optional[torch.Tensor] = None, dilation: int = 1, relu: bool = True,
+               res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dilated 3 x 3 convolution over the channel concatenation of a and (optionally) b, which is never built, with bias,
+    (relu) max(., 0) and an optional residual added last (m324_conv3x3_ex, fp32 MFMA): a [images,H,W,Ca], b [images,H,W,Cb],
+    Ca % 4 = Cb % 4 = 0; wp fp32 [conv_kpad(Ca + Cb), Cout] laid out as for conv3x3 with Cin = Ca + Cb; bias [Cout], Cout % 4 = 0;
+    res [images,H,W,Cout].  Returns fp32 [images,H,W,Cout] = act(conv + bias) + res."""
+    a = _nhwc(a, "conv3x3_ex: a")
+    n, H, W, ca = a.shape
+    cb = 0
+    if b is not None:
+        b = _nhwc(b, "conv3x3_ex: b")
+        if tuple(b.shape[:3]) != (n, H, W) or b.device != a.device:
+            raise L.M324Error(f"conv3x3_ex: b {tuple(b.shape)} does not match a {tuple(a.shape)}, or lives on another device")
+        cb = b.shape[3]
+    wp = _device_array(wp, torch.float32, "conv3x3_ex: wp")
+    bias = _device_array(bias, torch.float32, "conv3x3_ex: bias")
+    if ca + cb > CONV_MAX_CHANNELS or wp.dim() != 2 or wp.shape[0] != conv_kpad(ca + cb):
+        raise L.M324Error(f"conv3x3_ex: wp must be [{conv_kpad(ca + cb)},Cout] for Ca + Cb = {ca} + {cb} <= {CONV_MAX_CHANNELS}, got {tuple(wp.shape)}")
+    cout = wp.shape[1]
+    if cout % 4 or not 4 <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
+        raise L.M324Error(f"conv3x3_ex: Cout must be a multiple of 4 up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, "
+                          f"bias {tuple(bias.shape)}")
+    if not 1 <= int(dilation) <= CONV_MAX_DILATION:
+        raise L.M324Error(f"conv3x3_ex: dilation must be in 1..{CONV_MAX_DILATION}, got {dilation}")
+    if res is not None:
+        res = _device_array(res, torch.float32, "conv3x3_ex: res")
+        if tuple(res.shape) != (n, H, W, cout) or res.device != a.device:
+            raise L.M324Error(f"conv3x3_ex: res must be {(n, H, W, cout)} on a's device, got {tuple(res.shape)}")
+    out = _out_like(out, (n, H, W, cout), a.device, "conv3x3_ex")
+    _launch("m324_conv3x3_ex", _p(a), ca, _p(b), cb, _p(wp), _p(bias), _p(res), _p(out), n, H, W, cout, int(dilation), 1 if relu else 0)
+    _wrote(out)
+    return out
+
+
+def maxpool2x2_ceil(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """2 x 2, stride 2 max-pool with the window cut at the edge (MaxPool2d(2, 2, ceil_mode=True); m324_maxpool2x2_ceil): fp32
+    NHWC [images,H,W,C] -> [images,ceil(H/2),ceil(W/2),C]"""
+    x = _nhwc(x, "maxpool2x2_ceil: x")
+    n, H, W, c = x.shape
+    out = _out_like(out, (n, (H + 1) // 2, (W + 1) // 2, c), x.device, "maxpool2x2_ceil")
+    _launch("m324_maxpool2x2_ceil", _p(x), _p(out), n, H, W, c)
+    _wrote(out)
+    return out
+
+
+def upsample_bilinear(x: torch.Tensor, size, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bilinear resize, align_corners=False, of fp32 NHWC [images,H,W,C] to size = (Ho, Wo) (m324_upsample_bilinear; the
+    evaluation order is in include/m324.h) -> [images,Ho,Wo,C]"""
+    x = _nhwc(x, "upsample_bilinear: x")
+    n, H, W, c = x.shape
+    Ho, Wo = (int(v) for v in size)
+    if not (1 <= Ho <= MATTE_MAX_SIDE and 1 <= Wo <= MATTE_MAX_SIDE and H <= MATTE_MAX_SIDE and W <= MATTE_MAX_SIDE) or n * Ho * Wo >= 2 ** 31:
+        raise L.M324Error(f"upsample_bilinear: sizes must be in 1..{MATTE_MAX_SIDE} and images * Ho * Wo below 2^31, got {tuple(x.shape)} -> {(Ho, Wo)}")
+    out = _out_like(out, (n, Ho, Wo, c), x.device, "upsample_bilinear")
+    _launch("m324_upsample_bilinear", _p(x), _p(out), n, H, W, Ho, Wo, c)
+    _wrote(out)
+    return out
+
+
+def matte_prepare(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The matting network's input fp32 [images,H,W,4] (channel 3 is zero) from uint8 [images,H,W,3]: every frame divided by its
+    own largest byte, then the ImageNet mean and deviation, in float64 rounded once (m324_matte_prepare)."""
+    _on_device(src, "matte_prepare")
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or 0 in src.shape:
+        raise L.M324Error(f"matte_prepare: expected uint8 [images,H,W,3], got {src.dtype} {tuple(src.shape)}")
+    n, H, W = src.shape[:3]
+    if n * H * W >= 2 ** 31:
+        raise L.M324Error(f"matte_prepare: images * H * W must stay below 2^31, got {tuple(src.shape)}")
+    src = src.detach().contiguous()
+    out = _out_like(out, (n, H, W, 4), src.device, "matte_prepare")
+    frame_max = torch.empty((n,), dtype=torch.int32, device=src.device)
+    partial = torch.empty((n * MATTE_CHUNKS,), dtype=torch.int32, device=src.device)
+    _launch("m324_matte_prepare", _p(src), n, H, W, _p(partial), _p(frame_max), _p(out))
+    _wrote(out)
+    return out
+
+
+def matte_fuse(sides, weights, bias: float, size, *, want_logits: bool = False):
+    """The fused side-output head (m324_matte_fuse): sides six fp32 NHWC maps [images,h_k,w_k,C] whose channel 0 is the side
+    output, each at its own resolution; weights six floats and bias, the 1 x 1 `outconv` (host numbers).  Returns (prob fp32
+    [images,Ho,Wo] = sigmoid(d0), d0 or None)."""
+    if len(sides) != MATTE_SIDES or len(weights) != MATTE_SIDES:
+        raise L.M324Error(f"matte_fuse: expected {MATTE_SIDES} side maps and weights, got {len(sides)} and {len(weights)}")
+    sides = [_nhwc(s, f"matte_fuse: side {k}") for k, s in enumerate(sides)]
+    n, stride, dev = sides[0].shape[0], sides[0].shape[3], sides[0].device
+    Ho, Wo = (int(v) for v in size)
+    for k, s in enumerate(sides):
+        if s.shape[0] != n or s.shape[3] != stride or s.device != dev or s.shape[1] > Ho or s.shape[2] > Wo:
+            raise L.M324Error(f"matte_fuse: side {k} {tuple(s.shape)} must have {n} images and {stride} channels on one device and be no "
+                              f"larger than the output {(Ho, Wo)}")
+    if not (1 <= Ho <= MATTE_MAX_SIDE and 1 <= Wo <= MATTE_MAX_SIDE) or n * Ho * Wo >= 2 ** 31:
+        raise L.M324Error(f"matte_fuse: the output must be within {MATTE_MAX_SIDE} a side and images * Ho * Wo below 2^31, got {(n, Ho, Wo)}")
+    ptrs = (C.c_void_p * MATTE_SIDES)(*[s.data_ptr() for s in sides])
+    hs = (C.c_int * MATTE_SIDES)(*[s.shape[1] for s in sides])
+    ws = (C.c_int * MATTE_SIDES)(*[s.shape[2] for s in sides])
+    oc = (C.c_float * (MATTE_SIDES + 1))(*[float(w) for w in weights], float(bias))
+    prob = torch.empty((n, Ho, Wo), dtype=torch.float32, device=dev)
+    logit = torch.empty((n, Ho, Wo), dtype=torch.float32, device=dev) if want_logits else None
+    _launch("m324_matte_fuse", C.addressof(ptrs), C.addressof(hs), C.addressof(ws), stride, C.addressof(oc), n, Ho, Wo, _p(prob), _p(logit))
+    _wrote(prob, logit)
+    return prob, logit
+
+
+def matte_quantise(prob: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """The 8-bit matte of fp32 [images,H,W] probabilities (m324_matte_quantise): per frame (p - min) / (max - min) * 255,
+    truncated; a constant frame gives 0.  Returns (uint8 [images,H,W], fp32 [images,2] = the frame's min and max)."""
+    prob = _device_array(prob, torch.float32, "matte_quantise: prob")
+    if prob.dim() != 3 or 0 in prob.shape or prob.numel() >= 2 ** 31:
+        raise L.M324Error(f"matte_quantise: expected fp32 [images,H,W] with fewer than 2^31 values, got {tuple(prob.shape)}")
+    n, H, W = prob.shape
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=prob.device)
+    elif not _is_device(out) or out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous() or out.device != prob.device:
+        raise L.M324Error(f"matte_quantise: out must be a contiguous uint8 device tensor {(n, H, W)}")
+    minmax = torch.empty((n, 2), dtype=torch.float32, device=prob.device)
+    partial = torch.empty((n * MATTE_CHUNKS * 2,), dtype=torch.float32, device=prob.device)
+    _launch("m324_matte_quantise", _p(prob), n, H * W, _p(partial), _p(minmax), _p(out))
+    _wrote(out, minmax)
+    return out, minmax
+
+
 # ------------------------------------------------------------------------------------------------ training side
 def transpose(x: torch.Tensor, rows_pad: Optional[int] = None) -> torch.Tensor:
     """[R, C] -> [C, rows_pad] (rows_pad = round_up(R, 64) by default; the pad columns are zeros)."""
