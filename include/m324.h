@@ -648,12 +648,16 @@ int m324_render_shade_tex(const int* faces, int n_faces, int n_vertices, int fra
                           int* depth, void* scratch, long scratch_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Perceptual evaluation (csrc/perceptual.hip; added at ABI 23 without a bump): the pieces of LPIPS on a VGG16 trunk, what
- * motion324_amd/perceptual.py strings together.  replaces: lpips.LPIPS(net='vgg', spatial=True) of the reference's
- * evaluation/evaluation.py (torch / cuDNN there).  Everything is fp32, activations are NHWC ([images, H, W, C], C contiguous),
- * every pointer is device memory and 16-byte aligned unless said otherwise, and images * H * W stays below 2^31.
+ * Perceptual evaluation (csrc/perceptual.hip, and csrc/conv.hip for m324_conv3x3 and m324_maxpool2x2; added at ABI 23 without a
+ * bump): the pieces of LPIPS on a VGG16 trunk, what motion324_amd/perceptual.py strings together.  replaces:
+ * lpips.LPIPS(net='vgg', spatial=True) of the reference's evaluation/evaluation.py (torch / cuDNN there).  Everything is fp32,
+ * activations are NHWC ([images, H, W, C], C contiguous), every pointer is device memory and 16-byte aligned unless said
+ * otherwise, and images * H * W stays below 2^31.
  *
- * m324_conv3x3: out[i, y, x, n] = act(bias[n] + sum over taps t = 3 (dy + 1) + (dx + 1), dy, dx in -1..1, and channels c of
+ * m324_conv3x3: m324_conv3x3_ex (below) restricted to one input tensor (a = in, Ca = Cin, b = NULL), dilation 1, no residual and
+ *   Cout % 32 = 0 -- the same kernel behind the same host path, which words its refusals in Ca -- with a tile rule of its own
+ *   that never shows in the bits:
+ *   out[i, y, x, n] = act(bias[n] + sum over taps t = 3 (dy + 1) + (dx + 1), dy, dx in -1..1, and channels c of
  *   in[i, y + dy, x + dx, c] * wp[t * Cin + c][n]),  stride 1, a tap outside the image contributes 0 (zero padding of `in` itself),
  *   act = max(., 0) when relu = 1, the identity when relu = 0.
  *   Shape contract: Cin % 4 = 0, Cout % 32 = 0, both in 4 / 32 .. M324_CONV_MAX_CHANNELS; any H, W >= 1; any images >= 1.
@@ -665,7 +669,8 @@ int m324_render_shade_tex(const int* faces, int n_faces, int n_vertices, int fra
  *   output is act(s + bias).  (One chain over all k loses accuracy with the length of the running sum: at 9 Cin = 4608 the
  *   metric's deep layers came out up to 10 times further from fp64 than with runs of 144.)  An output's bits depend on its
  *   9 Cin inputs and the weights alone: not on the image's place in the batch, the tile, the grid or a second call.
- * m324_maxpool2x2: out[i, y, x, c] = max of in[i, 2y .. 2y + 1, 2x .. 2x + 1, c]; H and W even, C % 4 = 0.  Exact.
+ * m324_maxpool2x2: out[i, y, x, c] = max of in[i, 2y .. 2y + 1, 2x .. 2x + 1, c]; H and W even, C % 4 = 0.  Exact.  The kernel of
+ *   m324_maxpool2x2_ceil, which cuts no window at even sizes; odd sizes are refused here.
  * m324_lpips_prepare: the scaled input of the trunk, dst fp32 [images, H, W, 4]:  dst_c = (x_c - shift_c) / scale_c for c < 3 with
  *   shift (-.030, -.088, -.188), scale (.458, .448, .450), and dst_3 = 0.  mode M324_LPIPS_U8_NHWC: src uint8 [images, H, W, 3]
  *   (any alignment), x = ((float)v / 255) * 2 - 1.  mode M324_LPIPS_F32_NCHW: src fp32 [images, 3, H, W] (4-byte aligned),
@@ -694,14 +699,15 @@ int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Foreground matting (csrc/matting.hip; added at ABI 23 without a bump): the pieces of U2-Net and of the arithmetic the
- * `rembg` package wraps around it, what motion324_amd/matting.py strings together.  replaces: the per-frame
- * rembg.remove(frame, session='u2net') loop of the reference's utils/inference_utils.py:segment_foreground_with_u2net
- * (onnxruntime with a PIL round trip there).  Everything is fp32 unless said otherwise, activations are NHWC ([images, H, W, C],
+ * Foreground matting (csrc/matting.hip, and csrc/conv.hip for m324_conv3x3_ex, m324_conv3x3_ex_tile and m324_maxpool2x2_ceil;
+ * added at ABI 23 without a bump): the pieces of U2-Net and of the arithmetic the `rembg` package wraps around it, what
+ * motion324_amd/matting.py strings together.  replaces: the per-frame rembg.remove(frame, session='u2net') loop of the
+ * reference's utils/inference_utils.py:segment_foreground_with_u2net (onnxruntime with a PIL round trip there).  Everything is fp32 unless said otherwise, activations are NHWC ([images, H, W, C],
  * C contiguous), every pointer is device memory and 16-byte aligned unless said otherwise, images * H * W stays below 2^31.
  *
- * m324_conv3x3_ex: m324_conv3x3 generalised.  The input is the channel concatenation of a [images, H, W, Ca] and b [images, H,
- *   W, Cb] (a's channels first; b = NULL with Cb = 0 for one source), which is never built:
+ * m324_conv3x3_ex: the general 3 x 3 convolution, of which m324_conv3x3 is a restriction.  The input is the channel
+ *   concatenation of a [images, H, W, Ca] and b [images, H, W, Cb] (a's channels first; b = NULL with Cb = 0 for one source),
+ *   which is never built:
  *     s[i, y, x, n] = sum over taps t = 3 (dy + 1) + (dx + 1), dy, dx in -1..1, and channels c < Ca + Cb of
  *                     cat[i, y + dilation dy, x + dilation dx, c] * wp[t (Ca + Cb) + c][n],   a tap outside the image contributes 0,
  *     out = act(s + bias) + res  with act = max(., 0) when relu = 1 and res [images, H, W, Cout] optional (NULL: nothing added).
@@ -710,8 +716,8 @@ int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs
  *   convolution with fewer than four outputs (the side outputs: one) is packed with zero columns and a zero bias up to four.
  *   Arithmetic: that of m324_conv3x3, unchanged -- chains of M324_CONV_RUN consecutive k from 0 on v_mfma_f32_32x32x2_f32, the
  *   chains added in order, then + bias, the activation, + res (one rounding each).  With dilation 1, b = NULL and res = NULL the
- *   bits are those of m324_conv3x3 wherever that accepts the shape.  The tile (128 pixels by 128, 64 or 32 channels) is chosen
- *   from Cout and the pixel count -- m324_conv3x3_ex_tile (host only) returns its width -- and never shows in the bits, nor does
+ *   bits are those of m324_conv3x3 wherever that accepts the shape: it is the same kernel.  The tile (128 pixels by 128, 64 or
+ *   32 channels) is chosen from Cout and the pixel count -- m324_conv3x3_ex_tile (host only) returns its width -- and never shows in the bits, nor does
  *   the image's place in the batch, the grid or a second call.
  * m324_maxpool2x2_ceil: out[i, y, x, c] = max of in[i, 2y .. min(2y + 1, H - 1), 2x .. min(2x + 1, W - 1), c], out [images,
  *   ceil(H / 2), ceil(W / 2), C]: MaxPool2d(2, 2, ceil_mode=True).  C % 4 = 0.  Exact.

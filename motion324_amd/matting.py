@@ -34,7 +34,7 @@ import torch
 
 from . import framing, ops
 from .lib import M324Error
-from .perceptual import pack_conv_weight
+from .ops import pack_conv_weight
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)

@@ -1566,17 +1566,28 @@ def voxel_counts(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return counts
 
 
-# ------------------------------------------------------------------------------------------------ perceptual evaluation
+# ------------------------------------------------------------------------------------------------ convolution
+# the 3 x 3 convolution and the 2 x 2 pool that the perceptual evaluation and the foreground matting share (csrc/conv.hip)
 CONV_KPAD = 16                  # M324_CONV_KPAD: the packed weights have 9 Cin rows rounded up to this, zeros behind 9 Cin
 CONV_MAX_CHANNELS = 4096        # M324_CONV_MAX_CHANNELS
-LPIPS_MAX_CHANNELS = 1024       # M324_LPIPS_MAX_CHANNELS
-LPIPS_CHUNKS = 64               # M324_LPIPS_CHUNKS
-LPIPS_MODES = {"u8_nhwc": 0, "f32_nchw": 1}
+CONV_MAX_DILATION = 64          # M324_CONV_MAX_DILATION
 
 
 def conv_kpad(cin: int) -> int:
     """rows of the K-major weight matrix m324_conv3x3 reads for `cin` input channels"""
     return (9 * int(cin) + CONV_KPAD - 1) // CONV_KPAD * CONV_KPAD
+
+
+def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] (torch's layout) -> fp32 [Kpad, Cout] with row (3 ky + kx) * Cin4 + c, Cin4 = Cin rounded up to a multiple
+    of 4 (the pad channels are zero rows: the first layer's three channels become four) and zero rows up to Kpad."""
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    cin4 = (cin + 3) // 4 * 4
+    packed = torch.zeros((conv_kpad(cin4), cout), dtype=torch.float32)
+    taps = torch.zeros((9, cin4, cout), dtype=torch.float32)
+    taps[:, :cin] = w.detach().to(torch.float32).permute(2, 3, 1, 0).reshape(9, cin, cout)
+    packed[:9 * cin4] = taps.reshape(9 * cin4, cout)
+    return packed
 
 
 def _nhwc(x, name: str) -> torch.Tensor:
@@ -1596,22 +1607,62 @@ def _out_like(out, shape, device, name: str) -> torch.Tensor:
     return out
 
 
+def _conv_weights(wp, bias, cin: int, cin_text: str, multiple: int, name: str):
+    """wp [conv_kpad(cin), Cout] and bias [Cout] of the convolution `name`, Cout a multiple of `multiple`: (wp, bias, Cout)"""
+    wp = _device_array(wp, torch.float32, f"{name}: wp")
+    bias = _device_array(bias, torch.float32, f"{name}: bias")
+    if cin > CONV_MAX_CHANNELS or wp.dim() != 2 or wp.shape[0] != conv_kpad(cin):
+        raise L.M324Error(f"{name}: wp must be [{conv_kpad(cin)},Cout] for {cin_text}, got {tuple(wp.shape)}")
+    cout = wp.shape[1]
+    if cout % multiple or not multiple <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
+        raise L.M324Error(f"{name}: Cout must be a multiple of {multiple} up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, "
+                          f"bias {tuple(bias.shape)}")
+    return wp, bias, cout
+
+
 def conv3x3(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, relu: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """3 x 3 convolution, stride 1, zero padding 1, bias and (relu) max(., 0) (m324_conv3x3, fp32 MFMA): x fp32 NHWC
     [images,H,W,Cin], Cin % 4 = 0; wp fp32 [conv_kpad(Cin), Cout], row (3 (dy + 1) + dx + 1) * Cin + c, zeros behind 9 Cin
-    (perceptual.pack_conv_weight makes it); bias fp32 [Cout], Cout % 32 = 0.  Returns fp32 [images,H,W,Cout]."""
+    (pack_conv_weight makes it); bias fp32 [Cout], Cout % 32 = 0.  Returns fp32 [images,H,W,Cout]."""
     x = _nhwc(x, "conv3x3: x")
-    wp = _device_array(wp, torch.float32, "conv3x3: wp")
-    bias = _device_array(bias, torch.float32, "conv3x3: bias")
     n, H, W, cin = x.shape
-    if wp.dim() != 2 or wp.shape[0] != conv_kpad(cin):
-        raise L.M324Error(f"conv3x3: wp must be [{conv_kpad(cin)},Cout] for Cin {cin}, got {tuple(wp.shape)}")
-    cout = wp.shape[1]
-    if cout % 32 or not 32 <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
-        raise L.M324Error(f"conv3x3: Cout must be a multiple of 32 up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, "
-                          f"bias {tuple(bias.shape)}")
+    wp, bias, cout = _conv_weights(wp, bias, cin, f"Cin {cin}", 32, "conv3x3")
     out = _out_like(out, (n, H, W, cout), x.device, "conv3x3")
     _launch("m324_conv3x3", _p(x), _p(wp), _p(bias), _p(out), n, H, W, cin, cout, 1 if relu else 0)
+    _wrote(out)
+    return out
+
+
+def conv3x3_ex_tile(images: int, H: int, W: int, cout: int) -> int:
+    """output channels per workgroup tile (128, 64 or 32) m324_conv3x3_ex takes for this shape: host-only, never in the bits"""
+    n = int(L.load().m324_conv3x3_ex_tile(int(images), int(H), int(W), int(cout)))
+    L.check(0 if n > 0 else n, "m324_conv3x3_ex_tile")
+    return n
+
+
+def conv3x3_ex(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, b: Optional[torch.Tensor] = None, dilation: int = 1, relu: bool = True,
+               res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dilated 3 x 3 convolution over the channel concatenation of a and (optionally) b, which is never built, with bias,
+    (relu) max(., 0) and an optional residual added last (m324_conv3x3_ex, fp32 MFMA): a [images,H,W,Ca], b [images,H,W,Cb],
+    Ca % 4 = Cb % 4 = 0; wp fp32 [conv_kpad(Ca + Cb), Cout] laid out as for conv3x3 with Cin = Ca + Cb; bias [Cout], Cout % 4 = 0;
+    res [images,H,W,Cout].  Returns fp32 [images,H,W,Cout] = act(conv + bias) + res."""
+    a = _nhwc(a, "conv3x3_ex: a")
+    n, H, W, ca = a.shape
+    cb = 0
+    if b is not None:
+        b = _nhwc(b, "conv3x3_ex: b")
+        if tuple(b.shape[:3]) != (n, H, W) or b.device != a.device:
+            raise L.M324Error(f"conv3x3_ex: b {tuple(b.shape)} does not match a {tuple(a.shape)}, or lives on another device")
+        cb = b.shape[3]
+    wp, bias, cout = _conv_weights(wp, bias, ca + cb, f"Ca + Cb = {ca} + {cb} <= {CONV_MAX_CHANNELS}", 4, "conv3x3_ex")
+    if not 1 <= int(dilation) <= CONV_MAX_DILATION:
+        raise L.M324Error(f"conv3x3_ex: dilation must be in 1..{CONV_MAX_DILATION}, got {dilation}")
+    if res is not None:
+        res = _device_array(res, torch.float32, "conv3x3_ex: res")
+        if tuple(res.shape) != (n, H, W, cout) or res.device != a.device:
+            raise L.M324Error(f"conv3x3_ex: res must be {(n, H, W, cout)} on a's device, got {tuple(res.shape)}")
+    out = _out_like(out, (n, H, W, cout), a.device, "conv3x3_ex")
+    _launch("m324_conv3x3_ex", _p(a), ca, _p(b), cb, _p(wp), _p(bias), _p(res), _p(out), n, H, W, cout, int(dilation), 1 if relu else 0)
     _wrote(out)
     return out
 
@@ -1626,6 +1677,23 @@ def maxpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
     _launch("m324_maxpool2x2", _p(x), _p(out), n, H, W, c)
     _wrote(out)
     return out
+
+
+def maxpool2x2_ceil(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """2 x 2, stride 2 max-pool with the window cut at the edge (MaxPool2d(2, 2, ceil_mode=True); m324_maxpool2x2_ceil): fp32
+    NHWC [images,H,W,C] -> [images,ceil(H/2),ceil(W/2),C]"""
+    x = _nhwc(x, "maxpool2x2_ceil: x")
+    n, H, W, c = x.shape
+    out = _out_like(out, (n, (H + 1) // 2, (W + 1) // 2, c), x.device, "maxpool2x2_ceil")
+    _launch("m324_maxpool2x2_ceil", _p(x), _p(out), n, H, W, c)
+    _wrote(out)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ perceptual evaluation
+LPIPS_MAX_CHANNELS = 1024       # M324_LPIPS_MAX_CHANNELS
+LPIPS_CHUNKS = 64               # M324_LPIPS_CHUNKS
+LPIPS_MODES = {"u8_nhwc": 0, "f32_nchw": 1}
 
 
 def lpips_prepare(src: torch.Tensor, *, normalize: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1666,62 +1734,9 @@ def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: Option
 
 
 # ------------------------------------------------------------------------------------------------ foreground matting
-CONV_MAX_DILATION = 64          # M324_CONV_MAX_DILATION
 MATTE_SIDES = 6                 # M324_MATTE_SIDES
 MATTE_MAX_SIDE = 16384          # M324_MATTE_MAX_SIDE
 MATTE_CHUNKS = 64               # M324_MATTE_CHUNKS: runs per frame of the two-level per-frame reductions
-
-
-def conv3x3_ex_tile(images: int, H: int, W: int, cout: int) -> int:
-    """output channels per workgroup tile (128, 64 or 32) m324_conv3x3_ex takes for this shape: host-only, never in the bits"""
-    n = int(L.load().m324_conv3x3_ex_tile(int(images), int(H), int(W), int(cout)))
-    L.check(0 if n > 0 else n, "m324_conv3x3_ex_tile")
-    return n
-
-
-def conv3x3_ex(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, b: Optional[torch.Tensor] = None, dilation: int = 1, relu: bool = True,
-               res: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Dilated 3 x 3 convolution over the channel concatenation of a and (optionally) b, which is never built, with bias,
-    (relu) max(., 0) and an optional residual added last (m324_conv3x3_ex, fp32 MFMA): a [images,H,W,Ca], b [images,H,W,Cb],
-    Ca % 4 = Cb % 4 = 0; wp fp32 [conv_kpad(Ca + Cb), Cout] laid out as for conv3x3 with Cin = Ca + Cb; bias [Cout], Cout % 4 = 0;
-    res [images,H,W,Cout].  Returns fp32 [images,H,W,Cout] = act(conv + bias) + res."""
-    a = _nhwc(a, "conv3x3_ex: a")
-    n, H, W, ca = a.shape
-    cb = 0
-    if b is not None:
-        b = _nhwc(b, "conv3x3_ex: b")
-        if tuple(b.shape[:3]) != (n, H, W) or b.device != a.device:
-            raise L.M324Error(f"conv3x3_ex: b {tuple(b.shape)} does not match a {tuple(a.shape)}, or lives on another device")
-        cb = b.shape[3]
-    wp = _device_array(wp, torch.float32, "conv3x3_ex: wp")
-    bias = _device_array(bias, torch.float32, "conv3x3_ex: bias")
-    if ca + cb > CONV_MAX_CHANNELS or wp.dim() != 2 or wp.shape[0] != conv_kpad(ca + cb):
-        raise L.M324Error(f"conv3x3_ex: wp must be [{conv_kpad(ca + cb)},Cout] for Ca + Cb = {ca} + {cb} <= {CONV_MAX_CHANNELS}, got {tuple(wp.shape)}")
-    cout = wp.shape[1]
-    if cout % 4 or not 4 <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
-        raise L.M324Error(f"conv3x3_ex: Cout must be a multiple of 4 up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, "
-                          f"bias {tuple(bias.shape)}")
-    if not 1 <= int(dilation) <= CONV_MAX_DILATION:
-        raise L.M324Error(f"conv3x3_ex: dilation must be in 1..{CONV_MAX_DILATION}, got {dilation}")
-    if res is not None:
-        res = _device_array(res, torch.float32, "conv3x3_ex: res")
-        if tuple(res.shape) != (n, H, W, cout) or res.device != a.device:
-            raise L.M324Error(f"conv3x3_ex: res must be {(n, H, W, cout)} on a's device, got {tuple(res.shape)}")
-    out = _out_like(out, (n, H, W, cout), a.device, "conv3x3_ex")
-    _launch("m324_conv3x3_ex", _p(a), ca, _p(b), cb, _p(wp), _p(bias), _p(res), _p(out), n, H, W, cout, int(dilation), 1 if relu else 0)
-    _wrote(out)
-    return out
-
-
-def maxpool2x2_ceil(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """2 x 2, stride 2 max-pool with the window cut at the edge (MaxPool2d(2, 2, ceil_mode=True); m324_maxpool2x2_ceil): fp32
-    NHWC [images,H,W,C] -> [images,ceil(H/2),ceil(W/2),C]"""
-    x = _nhwc(x, "maxpool2x2_ceil: x")
-    n, H, W, c = x.shape
-    out = _out_like(out, (n, (H + 1) // 2, (W + 1) // 2, c), x.device, "maxpool2x2_ceil")
-    _launch("m324_maxpool2x2_ceil", _p(x), _p(out), n, H, W, c)
-    _wrote(out)
-    return out
 
 
 def upsample_bilinear(x: torch.Tensor, size, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -5,8 +5,8 @@ The image-space half of the reference's evaluation (evaluation/evaluation.py, `l
 relu1_2, relu2_2, relu3_3, relu4_3 and relu5_3, and per tap the channel-normalised squared difference weighted by a 1 x 1 layer.
 The score of a frame pair is the sum over the taps of the mean over that tap's own pixels: for sizes that are multiples of 16
 the reference's bilinear upsampling to H x W preserves the mean, so no upsampled map is built.  Everything is fp32 on the fp32
-MFMA (csrc/perceptual.hip; include/m324.h has the arithmetic).  The weights are the user's: a torchvision VGG16 state dict and
-the LPIPS package's `vgg.pth`, or the state dict of the reference's LPIPS module.
+MFMA (csrc/conv.hip, the head in csrc/perceptual.hip; include/m324.h has the arithmetic).  The weights are the user's: a
+torchvision VGG16 state dict and the LPIPS package's `vgg.pth`, or the state dict of the reference's LPIPS module.
 
     python -m motion324_amd.perceptual --gt_paths A ... --result_paths B ... --weights vgg16.pth [lin.pth] [--output_dir DIR]
 """
@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from .lib import M324Error
+from .ops import pack_conv_weight         # re-exported: perceptual.pack_conv_weight is the name tests and tools know
 
 # (input channels, output channels) of the thirteen convolutions; a pool follows each stage but the last
 STAGES = (((3, 64), (64, 64)), ((64, 128), (128, 128)), ((128, 256), (256, 256), (256, 256)),
@@ -54,18 +55,6 @@ LIN_KEYS = tuple(f"lin{k}.model.1.weight" for k in range(5))
 class LpipsWeights(NamedTuple):
     conv: tuple          # thirteen (wp fp32 [Kpad, Cout], bias fp32 [Cout]): the K-major layout of ops.conv3x3
     lin: tuple           # five fp32 [C]
-
-
-def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] (torch's layout) -> fp32 [Kpad, Cout] with row (3 ky + kx) * Cin4 + c, Cin4 = Cin rounded up to a multiple
-    of 4 (the pad channels are zero rows: the first layer's three channels become four) and zero rows up to Kpad."""
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    cin4 = (cin + 3) // 4 * 4
-    packed = torch.zeros((ops.conv_kpad(cin4), cout), dtype=torch.float32)
-    taps = torch.zeros((9, cin4, cout), dtype=torch.float32)
-    taps[:, :cin] = w.detach().to(torch.float32).permute(2, 3, 1, 0).reshape(9, cin, cout)
-    packed[:9 * cin4] = taps.reshape(9 * cin4, cout)
-    return packed
 
 
 def _load_file(path: str) -> dict:

@@ -32,7 +32,7 @@ def test_entry_points_are_declared_bound_and_built():
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
         assert name in lib.SIGNATURES and hasattr(lib.load(), name), name
     assert lib.ABI_VERSION == 23 and lib.load().m324_abi_version() == 23          # added entry points: no bump
-    assert "perceptual.hip" in build.SOURCES
+    assert "perceptual.hip" in build.SOURCES and "conv.hip" in build.SOURCES
     for macro, value in (("M324_CONV_KPAD", ops.CONV_KPAD), ("M324_CONV_MAX_CHANNELS", ops.CONV_MAX_CHANNELS),
                          ("M324_LPIPS_MAX_CHANNELS", ops.LPIPS_MAX_CHANNELS), ("M324_LPIPS_CHUNKS", ops.LPIPS_CHUNKS),
                          ("M324_LPIPS_U8_NHWC", ops.LPIPS_MODES["u8_nhwc"]), ("M324_LPIPS_F32_NCHW", ops.LPIPS_MODES["f32_nchw"])):

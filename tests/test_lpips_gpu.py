@@ -26,7 +26,8 @@ def _dev(frames):
 # ------------------------------------------------------------------------------------------------ the convolution alone
 @pytest.mark.parametrize("images", [1, 3])
 @pytest.mark.parametrize("H,W", [(1, 1), (2, 2), (5, 7), (16, 24)])
-@pytest.mark.parametrize("cin,cout", [(4, 64), (64, 64), (64, 128), (256, 512), (512, 512)])
+# Cout = 32 is a 64-wide tile with half its columns past Cout, Cout = 96 one with a ragged second column tile
+@pytest.mark.parametrize("cin,cout", [(4, 64), (64, 64), (64, 128), (256, 512), (512, 512), (8, 32), (4, 96)])
 def test_conv3x3_elementwise(cin, cout, H, W, images):
     g = torch.Generator().manual_seed(cin * 7 + cout * 3 + H * 11 + images)
     x = torch.randn((images, cin, H, W), generator=g) + 0.5                 # a non-zero mean: a wrong border shows
@@ -48,6 +49,14 @@ def test_conv3x3_elementwise(cin, cout, H, W, images):
         pooled = ops.maxpool2x2(out)
         EB.assert_within(pooled, to_nhwc(F.max_pool2d(ref.clamp_min(0), 2, 2)), to_nhwc(F.max_pool2d(bound, 2, 2)), what + " pooled")
         assert torch.equal(pooled.cpu(), to_nhwc(F.max_pool2d(out.cpu().permute(0, 3, 1, 2), 2, 2)))       # the pool adds no error
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (4, 6), (16, 24)])
+def test_maxpool2x2_is_the_ceil_pool_at_even_sizes(H, W):
+    g = torch.Generator().manual_seed(H * 13 + W)
+    x = (torch.randn((3, H, W, 8), generator=g) - 1.0).to(DEV)              # mostly negative: a zero-padded window would win
+    out = ops.maxpool2x2(x)
+    assert out.shape == (3, H // 2, W // 2, 8) and torch.equal(out, ops.maxpool2x2_ceil(x))
 
 
 @pytest.mark.parametrize("channels,pixels", [(4, 1), (96, 65), (200, 130), (1024, 4200)])

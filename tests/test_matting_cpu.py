@@ -29,7 +29,7 @@ def test_entry_points_are_declared_bound_and_built():
         assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
         assert name in lib.SIGNATURES and hasattr(lib.load(), name), name
     assert lib.ABI_VERSION == 23 and lib.load().m324_abi_version() == 23          # added entry points: no bump
-    assert "matting.hip" in build.SOURCES
+    assert "matting.hip" in build.SOURCES and "conv.hip" in build.SOURCES
     for macro, value in (("M324_CONV_MAX_DILATION", ops.CONV_MAX_DILATION), ("M324_MATTE_SIDES", ops.MATTE_SIDES),
                          ("M324_MATTE_MAX_SIDE", ops.MATTE_MAX_SIDE), ("M324_MATTE_CHUNKS", ops.MATTE_CHUNKS)):
         assert int(re.search(r"#define\s+" + macro + r"\s+(\d+)", header).group(1)) == value, macro
