@@ -741,6 +741,24 @@ int m324_lpips_layer(const float* fa, const float* fb, const float* w, int pairs
  * m324_matte_quantise: p fp32 [images, pixels] -> q uint8: per frame mi = min p, ma = max p (exact in any order; written to
  *   minmax fp32 [images, 2]), q = (uint8)(((p - mi) / (ma - mi)) * 255) in fp32 as written, truncated.  A frame with ma = mi
  *   (numpy: NaN) gives q = 0.  partial: scratch of images * M324_MATTE_CHUNKS * 2 floats, the two levels of m324_matte_prepare.
+ *
+ * ISNet (the IS-Net of DIS; `rembg`'s session 'isnet-general-use', which the reference's utils/rmbg_for_black_bg.py and
+ * scripts/hunyuan_Gen.py select; added at ABI 23 without a bump) is built from the same blocks and needs three more pieces:
+ * m324_conv3x3_s2: the stem, Conv2d(Cin, Cout, 3, stride=2, padding=1).  in [images, H, W, Cin] -> out [images, Ho, Wo, Cout] with
+ *   Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1:
+ *     out[i, y, x, n] = act(bias[n] + sum over taps t and channels c of in[i, 2y + dy, 2x + dx, c] * wp[t Cin + c][n]),
+ *   a tap outside the image contributes 0.  Shape contract: m324_conv3x3_ex's for one source (Cin % 4 = 0, Cout % 4 = 0, any H, W,
+ *   images >= 1; images * H * W below 2^31); wp as there.  It is the kernel of m324_conv3x3_ex with a compile-time gather: the same
+ *   chains of M324_CONV_RUN consecutive k from 0 on v_mfma_f32_32x32x2_f32, added in order, then + bias, then the activation.  The
+ *   tile is m324_conv3x3_ex's rule on the OUTPUT pixel count and never shows in the bits.  Consequence: with zero padding 1,
+ *   conv3x3_s2(x) has the bits of conv3x3_ex(x)[:, ::2, ::2] (one source, dilation 1, no residual).
+ * m324_matte_prepare_ex: m324_matte_prepare with given constants.  mean_std: HOST array of six doubles, mean_0..2 then std_0..2;
+ *   dst_c = (float)(((double)v_c / m - mean_c) / std_c), in float64 as written; every std finite and above 0, every mean finite
+ *   (checked on the host).  m324_matte_prepare is this call with (.485, .456, .406, .229, .224, .225): one kernel, the same bits.
+ * m324_matte_side: the one-map head.  side fp32 [images, side_h, side_w, side_stride] of which channel 0 is read (4-byte aligned).
+ *   Per output pixel of [images, Ho, Wo], Ho >= side_h, Wo >= side_w: d1 = that channel sampled by the rule of
+ *   m324_upsample_bilinear, the same operations in the same order, nothing contracted -- the bits of channel 0 of its output,
+ *   which is never written; prob = 1 / (1 + expf(-d1)); logit (optional) receives d1.
  * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.  No
  * atomics anywhere: every result is a fixed sequence of operations.
  * ------------------------------------------------------------------------------------------ */
@@ -758,6 +776,12 @@ int m324_matte_prepare(const unsigned char* src, int images, int H, int W, int* 
 int m324_matte_fuse(const float* const* sides, const int* side_h, const int* side_w, int side_stride, const float* outconv, int images,
                     int Ho, int Wo, float* prob, float* logit, void* stream);
 int m324_matte_quantise(const float* p, int images, long pixels, float* partial, float* minmax, unsigned char* q, void* stream);
+int m324_conv3x3_s2(const float* in, const float* wp, const float* bias, float* out, int images, int H, int W, int Cin, int Cout, int relu,
+                    void* stream);
+int m324_matte_prepare_ex(const unsigned char* src, int images, int H, int W, const double* mean_std, int* partial, int* frame_max, float* dst,
+                          void* stream);
+int m324_matte_side(const float* side, int side_h, int side_w, int side_stride, int images, int Ho, int Wo, float* prob, float* logit,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one

@@ -28,6 +28,12 @@
 // 64-channel layers and lost 4 to 10 % against 128 x 64 (184 VGPRs and 45 KB of LDS: fewer waves per CU); profiles/matting.md has
 // the numbers.  An output's bits do not depend on the tile: every tile runs the same chain for it.  The two entry points differ in
 // the rule that picks the tile (below, at the entry points) and in what they accept, in nothing else.
+//
+// m324_conv3x3_s2 (ISNet's stem) is the same kernel with one more compile-time parameter, STRIDE = 2: the pixels of M, of the tiles
+// and of the epilogue are those of the OUTPUT [images, Ho, Wo], and the prologue turns each into the source pixel (2 y, 2 x) it is
+// centred on; from there the fetch is the one above, bounds against (H, W) included.  So an output runs the chain that the stride-1
+// kernel runs for the source pixel (2 y, 2 x), and has its bits.  STRIDE = 1 compiles to the code it was: the gather is an `if
+// constexpr` in the prologue.
 #include "common.h"
 
 namespace {
@@ -43,7 +49,7 @@ __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.
 // WN waves along the channels, 4 / WN along the pixels.  PLAIN is m324_conv3x3's call (one source, dilation 1, no residual) with
 // b, Cb, dil and res folded away at compile time: the general kernel was measured 1.3 % slower on LPIPS without it
 // (profiles/conv_unified.md).  The operations on the data and their order are the same.
-template <int BN, int WN, bool PLAIN>
+template <int BN, int WN, bool PLAIN, int STRIDE>
 __global__ __launch_bounds__(THREADS) void conv3x3_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ wp,
                                                           const float* __restrict__ bias, const float* __restrict__ res, float* __restrict__ out,
                                                           long M, int H, int W, int Ca, int Cb, int Cout, int K, int n_tiles, int dil, int relu) {
@@ -72,8 +78,15 @@ __global__ __launch_bounds__(THREADS) void conv3x3_kernel(const float* __restric
         const long p = m0 + (tid >> 2) + 64 * i;
         pv[i] = p < M;
         pix[i] = pv[i] ? p : 0;
-        px[i] = (int)(pix[i] % W);
-        py[i] = (int)((pix[i] / W) % H);
+        if constexpr (STRIDE == 1) {
+            px[i] = (int)(pix[i] % W);
+            py[i] = (int)((pix[i] / W) % H);
+        } else {                                    // p counts output pixels; pix, px, py become the source pixel it is centred on
+            const int Ho = (H - 1) / STRIDE + 1, Wo = (W - 1) / STRIDE + 1;
+            px[i] = (int)(pix[i] % Wo) * STRIDE;
+            py[i] = (int)((pix[i] / Wo) % Ho) * STRIDE;
+            pix[i] = ((pix[i] / ((long)Wo * Ho)) * H + py[i]) * W + px[i];
+        }
     }
     int bk[BQ], bn[BQ];
     bool bv[BQ];
@@ -212,9 +225,10 @@ int tile_of(long M, int Cout) {
     return Cout > 32 ? 64 : 32;
 }
 
-// The contract both convolutions share, then the launch with the tile `width` (128, 64 or 32) that the caller `name` chose;
-// `plain` (m324_conv3x3: b, res null, dilation 1, width 128 or 64) takes the kernels with those folded away
-int conv3x3(const char* name, int width, bool plain, const float* a, int Ca, const float* b, int Cb, const float* wp, const float* bias,
+// The contract the convolutions share, then the launch with the tile `width` (128, 64 or 32) that the caller `name` chose;
+// `plain` (m324_conv3x3: b, res null, dilation 1, width 128 or 64) takes the kernels with those folded away; `stride` 2
+// (m324_conv3x3_s2, never plain) counts M, the tiles and the grid in output pixels
+int conv3x3(const char* name, int width, bool plain, int stride, const float* a, int Ca, const float* b, int Cb, const float* wp, const float* bias,
             const float* res, float* out, int images, int H, int W, int Cout, int dilation, int relu, void* stream) {
     M324_REQUIRE(a && wp && bias && out, "%s: null a, wp, bias or out", name);
     M324_REQUIRE(images >= 1 && H >= 1 && W >= 1, "%s: images, H and W must be at least 1, got %d, %d, %d", name, images, H, W);
@@ -224,8 +238,9 @@ int conv3x3(const char* name, int width, bool plain, const float* a, int Ca, con
     M324_REQUIRE(Cout >= 4 && Cout % 4 == 0, "%s: Cout must be a positive multiple of 4, got %d", name, Cout);
     M324_REQUIRE(Ca <= M324_CONV_MAX_CHANNELS && Cb <= M324_CONV_MAX_CHANNELS && Ca + Cb <= M324_CONV_MAX_CHANNELS && Cout <= M324_CONV_MAX_CHANNELS,
                  "%s: at most %d channels (Ca + Cb, and Cout), got Ca %d, Cb %d, Cout %d", name, M324_CONV_MAX_CHANNELS, Ca, Cb, Cout);
-    const long M = (long)images * H * W;
-    M324_REQUIRE(M <= 0x7fffffffL && (long)H * W <= 0x7fffffffL, "%s: images * H * W must stay below 2^31, got %ld", name, M);
+    M324_REQUIRE((long)images * H * W <= 0x7fffffffL && (long)H * W <= 0x7fffffffL, "%s: images * H * W must stay below 2^31, got %ld", name,
+                 (long)images * H * W);
+    const long M = (long)images * ((H - 1) / stride + 1) * ((W - 1) / stride + 1);
     M324_REQUIRE(dilation >= 1 && dilation <= M324_CONV_MAX_DILATION, "%s: dilation must be in 1..%d, got %d", name, M324_CONV_MAX_DILATION, dilation);
     M324_REQUIRE(aligned16(a) && aligned16(b) && aligned16(wp) && aligned16(out), "%s: a, b, wp and out must be 16-byte aligned", name);
     M324_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)res & 3) == 0, "%s: bias and res must be 4-byte aligned", name);
@@ -234,19 +249,25 @@ int conv3x3(const char* name, int width, bool plain, const float* a, int Ca, con
     const int n_tiles = (Cout + width - 1) / width;
     const dim3 grid((unsigned)((M + BM - 1) / BM * n_tiles));
     hipStream_t st = (hipStream_t)stream;
-#define M324_CONV_LAUNCH(BN_, WN_, PLAIN_)                                                                                                          \
-    hipLaunchKernelGGL((conv3x3_kernel<BN_, WN_, PLAIN_>), grid, dim3(THREADS), 0, st, a, b, wp, bias, res, out, M, H, W, Ca, Cb, Cout, K, n_tiles, \
-                       dilation, relu)
-    if (plain && width == 128)
-        M324_CONV_LAUNCH(128, 2, true);
+#define M324_CONV_LAUNCH(BN_, WN_, PLAIN_, STRIDE_)                                                                                            \
+    hipLaunchKernelGGL((conv3x3_kernel<BN_, WN_, PLAIN_, STRIDE_>), grid, dim3(THREADS), 0, st, a, b, wp, bias, res, out, M, H, W, Ca, Cb, Cout, K, \
+                       n_tiles, dilation, relu)
+    if (stride == 2 && width == 128)
+        M324_CONV_LAUNCH(128, 2, false, 2);
+    else if (stride == 2 && width == 64)
+        M324_CONV_LAUNCH(64, 2, false, 2);
+    else if (stride == 2)
+        M324_CONV_LAUNCH(32, 1, false, 2);
+    else if (plain && width == 128)
+        M324_CONV_LAUNCH(128, 2, true, 1);
     else if (plain)
-        M324_CONV_LAUNCH(64, 2, true);
+        M324_CONV_LAUNCH(64, 2, true, 1);
     else if (width == 128)
-        M324_CONV_LAUNCH(128, 2, false);
+        M324_CONV_LAUNCH(128, 2, false, 1);
     else if (width == 64)
-        M324_CONV_LAUNCH(64, 2, false);
+        M324_CONV_LAUNCH(64, 2, false, 1);
     else
-        M324_CONV_LAUNCH(32, 1, false);
+        M324_CONV_LAUNCH(32, 1, false, 1);
 #undef M324_CONV_LAUNCH
     M324_CHECK_LAUNCH(name);
     return M324_OK;
@@ -273,12 +294,20 @@ int maxpool2x2(const char* name, const float* in, float* out, int images, int H,
 extern "C" int m324_conv3x3(const float* in, const float* wp, const float* bias, float* out, int images, int H, int W, int Cin, int Cout,
                             int relu, void* stream) {
     M324_REQUIRE(Cout >= 32 && Cout % 32 == 0, "m324_conv3x3: Cout must be a positive multiple of 32, got %d", Cout);
-    return conv3x3("m324_conv3x3", Cout % 128 == 0 ? 128 : 64, true, in, Cin, nullptr, 0, wp, bias, nullptr, out, images, H, W, Cout, 1, relu, stream);
+    return conv3x3("m324_conv3x3", Cout % 128 == 0 ? 128 : 64, true, 1, in, Cin, nullptr, 0, wp, bias, nullptr, out, images, H, W, Cout, 1, relu, stream);
 }
 
 extern "C" int m324_conv3x3_ex(const float* a, int Ca, const float* b, int Cb, const float* wp, const float* bias, const float* res, float* out,
                                int images, int H, int W, int Cout, int dilation, int relu, void* stream) {
-    return conv3x3("m324_conv3x3_ex", tile_of((long)images * H * W, Cout), false, a, Ca, b, Cb, wp, bias, res, out, images, H, W, Cout, dilation, relu, stream);
+    return conv3x3("m324_conv3x3_ex", tile_of((long)images * H * W, Cout), false, 1, a, Ca, b, Cb, wp, bias, res, out, images, H, W, Cout, dilation, relu, stream);
+}
+
+// stride 2, zero padding 1: one source, no residual; the tile rule is m324_conv3x3_ex's on the OUTPUT pixel count
+extern "C" int m324_conv3x3_s2(const float* in, const float* wp, const float* bias, float* out, int images, int H, int W, int Cin, int Cout,
+                               int relu, void* stream) {
+    M324_REQUIRE(images >= 1 && H >= 1 && W >= 1, "m324_conv3x3_s2: images, H and W must be at least 1, got %d, %d, %d", images, H, W);
+    const long Mo = (long)images * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1);
+    return conv3x3("m324_conv3x3_s2", tile_of(Mo, Cout), false, 2, in, Cin, nullptr, 0, wp, bias, nullptr, out, images, H, W, Cout, 1, relu, stream);
 }
 
 extern "C" int m324_conv3x3_ex_tile(int images, int H, int W, int Cout) {

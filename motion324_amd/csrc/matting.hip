@@ -1,5 +1,5 @@
-// Foreground matting (U2-Net): the bilinear upsample, the input normalisation, the fused side-output head and the quantisation
-// of the matte.  The network's 3 x 3 convolution and its ceil-mode pool are in csrc/conv.hip.  The contract of every entry point
+// Foreground matting (U2-Net and ISNet): the bilinear upsample, the input normalisation, the fused side-output head of U2-Net, the
+// one-map head of ISNet and the quantisation of the matte.  The networks' 3 x 3 convolutions and their ceil-mode pool are in csrc/conv.hip.  The contract of every entry point
 // is in include/m324.h; what is here is how.
 #include "common.h"
 #include <math.h>
@@ -85,16 +85,23 @@ __global__ __launch_bounds__(64) void frame_bytemax_finish_kernel(const int* __r
     frame_max[img] = m;
 }
 
-// x_c = (v_c / m - mean_c) / std_c in float64, rounded once to fp32: what numpy computes for the same bytes
+struct MeanStd {
+    double mean[3], std[3];
+};
+
+// x_c = (v_c / m - mean_c) / std_c in float64, rounded once to fp32: what numpy computes for the same bytes.  The constants are
+// arguments (U2-Net's session and the DIS session of `rembg` differ in them); an IEEE division by a number known only at run time
+// has the bits of the division by the same literal.
 __global__ __launch_bounds__(THREADS) void matte_prepare_kernel(const unsigned char* __restrict__ src, const int* __restrict__ frame_max, long total,
-                                                                long HW, float4* __restrict__ dst) {
+                                                                long HW, MeanStd c, float4* __restrict__ dst) {
 #pragma clang fp contract(off)
     const long i = (long)blockIdx.x * THREADS + threadIdx.x;
     if (i >= total) return;
     const int fm = frame_max[i / HW];
     const double m = fm > 0 ? (double)fm : 1e-6;
     const unsigned char* s = src + 3 * i;
-    const double x0 = ((double)s[0] / m - 0.485) / 0.229, x1 = ((double)s[1] / m - 0.456) / 0.224, x2 = ((double)s[2] / m - 0.406) / 0.225;
+    const double x0 = ((double)s[0] / m - c.mean[0]) / c.std[0], x1 = ((double)s[1] / m - c.mean[1]) / c.std[1],
+                 x2 = ((double)s[2] / m - c.mean[2]) / c.std[2];
     dst[i] = make_float4((float)x0, (float)x1, (float)x2, 0.f);
 }
 
@@ -127,6 +134,24 @@ __global__ __launch_bounds__(THREADS) void matte_fuse_kernel(FuseArgs fa, int st
     d0 = d0 + fa.bias;
     if (logit) logit[i] = d0;
     prob[i] = 1.0f / (1.0f + expf(-d0));
+}
+
+// ISNet's head: the one side map sampled at the output's pixel, then the sigmoid; the upsampled map itself is never written
+__global__ __launch_bounds__(THREADS) void matte_side_kernel(const float* __restrict__ side, int h, int w, int stride, long total, int Ho, int Wo,
+                                                             float* __restrict__ prob, float* __restrict__ logit) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int x = (int)(i % Wo);
+    const long r = i / Wo;
+    const int y = (int)(r % Ho);
+    const long img = r / Ho;
+    const Lerp ly = lerp_of(y, h, Ho), lx = lerp_of(x, w, Wo);
+    const float* s = side + img * h * w * stride;
+    const float d1 = bilerp(s[((long)ly.i0 * w + lx.i0) * stride], s[((long)ly.i0 * w + lx.i1) * stride], s[((long)ly.i1 * w + lx.i0) * stride],
+                            s[((long)ly.i1 * w + lx.i1) * stride], ly, lx);
+    if (logit) logit[i] = d1;
+    prob[i] = 1.0f / (1.0f + expf(-d1));
 }
 
 // the smallest and the largest value of every run of every frame
@@ -208,21 +233,62 @@ extern "C" int m324_upsample_bilinear(const float* in, float* out, int images, i
     return M324_OK;
 }
 
-extern "C" int m324_matte_prepare(const unsigned char* src, int images, int H, int W, int* partial, int* frame_max, float* dst, void* stream) {
-    M324_REQUIRE(src && partial && frame_max && dst, "m324_matte_prepare: null src, partial, frame_max or dst");
+namespace {
+
+// both entry points of the normalisation: the contract, then the three launches
+int matte_prepare(const char* name, const unsigned char* src, int images, int H, int W, const double* mean_std, int* partial, int* frame_max,
+                  float* dst, void* stream) {
+    M324_REQUIRE(src && partial && frame_max && dst, "%s: null src, partial, frame_max or dst", name);
     M324_REQUIRE(images >= 1 && H >= 1 && W >= 1 && (long)images * H * W <= 0x7fffffffL,
-                 "m324_matte_prepare: images, H, W >= 1 and images * H * W below 2^31, got %d, %d, %d", images, H, W);
+                 "%s: images, H, W >= 1 and images * H * W below 2^31, got %d, %d, %d", name, images, H, W);
     M324_REQUIRE(aligned16(dst) && (((uintptr_t)frame_max | (uintptr_t)partial) & 3) == 0,
-                 "m324_matte_prepare: dst must be 16-byte, partial and frame_max 4-byte aligned");
+                 "%s: dst must be 16-byte, partial and frame_max 4-byte aligned", name);
+    MeanStd c;
+    for (int k = 0; k < 3; ++k) {
+        M324_REQUIRE(isfinite(mean_std[k]), "%s: mean %d is not finite", name, k);
+        M324_REQUIRE(isfinite(mean_std[3 + k]) && mean_std[3 + k] > 0.0, "%s: std %d must be finite and above 0, got %g", name, k, mean_std[3 + k]);
+        c.mean[k] = mean_std[k];
+        c.std[k] = mean_std[3 + k];
+    }
     const long HW = (long)H * W, total = images * HW;
     hipStream_t st = (hipStream_t)stream;
     const int chunks = chunks_of(3 * HW);
     hipLaunchKernelGGL(frame_bytemax_kernel, dim3((unsigned)((long)images * chunks)), dim3(THREADS), 0, st, src, 3 * HW, chunks, partial);
-    M324_CHECK_LAUNCH("m324_matte_prepare");
+    M324_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(frame_bytemax_finish_kernel, dim3((unsigned)((images + 63) / 64)), dim3(64), 0, st, (const int*)partial, images, chunks, frame_max);
-    M324_CHECK_LAUNCH("m324_matte_prepare");
-    hipLaunchKernelGGL(matte_prepare_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, st, src, (const int*)frame_max, total, HW, (float4*)dst);
-    M324_CHECK_LAUNCH("m324_matte_prepare");
+    M324_CHECK_LAUNCH(name);
+    hipLaunchKernelGGL(matte_prepare_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, st, src, (const int*)frame_max, total, HW, c, (float4*)dst);
+    M324_CHECK_LAUNCH(name);
+    return M324_OK;
+}
+
+}  // namespace
+
+extern "C" int m324_matte_prepare(const unsigned char* src, int images, int H, int W, int* partial, int* frame_max, float* dst, void* stream) {
+    static const double imagenet[6] = {0.485, 0.456, 0.406, 0.229, 0.224, 0.225};
+    return matte_prepare("m324_matte_prepare", src, images, H, W, imagenet, partial, frame_max, dst, stream);
+}
+
+extern "C" int m324_matte_prepare_ex(const unsigned char* src, int images, int H, int W, const double* mean_std, int* partial, int* frame_max,
+                                     float* dst, void* stream) {
+    M324_REQUIRE(mean_std, "m324_matte_prepare_ex: null mean_std");
+    return matte_prepare("m324_matte_prepare_ex", src, images, H, W, mean_std, partial, frame_max, dst, stream);
+}
+
+extern "C" int m324_matte_side(const float* side, int side_h, int side_w, int side_stride, int images, int Ho, int Wo, float* prob, float* logit,
+                               void* stream) {
+    M324_REQUIRE(side && prob, "m324_matte_side: null side or prob");
+    M324_REQUIRE(images >= 1 && Ho >= 1 && Wo >= 1 && Ho <= M324_MATTE_MAX_SIDE && Wo <= M324_MATTE_MAX_SIDE && (long)images * Ho * Wo <= 0x7fffffffL,
+                 "m324_matte_side: images >= 1, Ho and Wo in 1..%d, images * Ho * Wo below 2^31, got %d, %d, %d", M324_MATTE_MAX_SIDE, images, Ho, Wo);
+    M324_REQUIRE(side_stride >= 1 && side_stride <= M324_CONV_MAX_CHANNELS, "m324_matte_side: side_stride must be in 1..%d, got %d",
+                 M324_CONV_MAX_CHANNELS, side_stride);
+    M324_REQUIRE(side_h >= 1 && side_w >= 1 && side_h <= Ho && side_w <= Wo,
+                 "m324_matte_side: the side map must be between 1 x 1 and the output's %d x %d, got %d x %d", Ho, Wo, side_h, side_w);
+    M324_REQUIRE((((uintptr_t)side | (uintptr_t)prob | (uintptr_t)logit) & 3) == 0, "m324_matte_side: side, prob and logit must be 4-byte aligned");
+    const long total = (long)images * Ho * Wo;
+    hipLaunchKernelGGL(matte_side_kernel, dim3(blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, side, side_h, side_w, side_stride, total, Ho, Wo,
+                       prob, logit);
+    M324_CHECK_LAUNCH("m324_matte_side");
     return M324_OK;
 }
 

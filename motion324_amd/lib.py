@@ -131,6 +131,9 @@ SIGNATURES = {
     "m324_matte_prepare": [_P, _I, _I, _I, _P, _P, _P, _P],
     "m324_matte_fuse": [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "m324_matte_quantise": [_P, _I, _L, _P, _P, _P, _P],
+    "m324_conv3x3_s2": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "m324_matte_prepare_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "m324_matte_side": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "m324_transpose": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_colsum": [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "m324_colsum_multi": [C.POINTER(ColsumItem), _I, _P],

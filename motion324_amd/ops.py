@@ -7,6 +7,7 @@ live on a HIP device -- there is deliberately no CPU / eager fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -1667,6 +1668,19 @@ def conv3x3_ex(a: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, b: Opti
     return out
 
 
+def conv3x3_s2(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, relu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3 x 3 convolution with stride 2 and zero padding 1, bias and (relu) max(., 0) (m324_conv3x3_s2, the kernel of conv3x3_ex with
+    a strided gather): x fp32 NHWC [images,H,W,Cin], Cin % 4 = 0; wp, bias as for conv3x3_ex with one source, Cout % 4 = 0.  Returns
+    fp32 [images,(H - 1) // 2 + 1,(W - 1) // 2 + 1,Cout], the bits of conv3x3_ex(x, wp, bias, relu=relu)[:, ::2, ::2]."""
+    x = _nhwc(x, "conv3x3_s2: x")
+    n, H, W, cin = x.shape
+    wp, bias, cout = _conv_weights(wp, bias, cin, f"Cin {cin}", 4, "conv3x3_s2")
+    out = _out_like(out, (n, (H - 1) // 2 + 1, (W - 1) // 2 + 1, cout), x.device, "conv3x3_s2")
+    _launch("m324_conv3x3_s2", _p(x), _p(wp), _p(bias), _p(out), n, H, W, cin, cout, 1 if relu else 0)
+    _wrote(out)
+    return out
+
+
 def maxpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """2 x 2, stride 2 max-pool of fp32 NHWC [images,H,W,C] with even H, W (m324_maxpool2x2) -> [images,H/2,W/2,C]"""
     x = _nhwc(x, "maxpool2x2: x")
@@ -1753,10 +1767,17 @@ def upsample_bilinear(x: torch.Tensor, size, out: Optional[torch.Tensor] = None)
     return out
 
 
-def matte_prepare(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def matte_prepare(src: torch.Tensor, out: Optional[torch.Tensor] = None, mean=None, std=None) -> torch.Tensor:
     """The matting network's input fp32 [images,H,W,4] (channel 3 is zero) from uint8 [images,H,W,3]: every frame divided by its
-    own largest byte, then the ImageNet mean and deviation, in float64 rounded once (m324_matte_prepare)."""
+    own largest byte, then (. - mean) / std, in float64 rounded once.  mean = std = None: the ImageNet constants
+    (m324_matte_prepare); both given, three numbers each, std > 0: m324_matte_prepare_ex."""
     _on_device(src, "matte_prepare")
+    if (mean is None) != (std is None):
+        raise L.M324Error("matte_prepare: give mean and std together, or neither")
+    if mean is not None:
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3 or not all(math.isfinite(v) for v in mean) or not all(math.isfinite(v) and v > 0 for v in std):
+            raise L.M324Error(f"matte_prepare: mean and std must be three finite numbers each, every std above 0, got {mean} and {std}")
     if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3 or 0 in src.shape:
         raise L.M324Error(f"matte_prepare: expected uint8 [images,H,W,3], got {src.dtype} {tuple(src.shape)}")
     n, H, W = src.shape[:3]
@@ -1766,9 +1787,29 @@ def matte_prepare(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     out = _out_like(out, (n, H, W, 4), src.device, "matte_prepare")
     frame_max = torch.empty((n,), dtype=torch.int32, device=src.device)
     partial = torch.empty((n * MATTE_CHUNKS,), dtype=torch.int32, device=src.device)
-    _launch("m324_matte_prepare", _p(src), n, H, W, _p(partial), _p(frame_max), _p(out))
+    if mean is None:
+        _launch("m324_matte_prepare", _p(src), n, H, W, _p(partial), _p(frame_max), _p(out))
+    else:
+        ms = (C.c_double * 6)(*mean, *std)
+        _launch("m324_matte_prepare_ex", _p(src), n, H, W, C.addressof(ms), _p(partial), _p(frame_max), _p(out))
     _wrote(out)
     return out
+
+
+def matte_side(side: torch.Tensor, size, *, want_logits: bool = False):
+    """The one-map head (m324_matte_side): side fp32 NHWC [images,h,w,C] whose channel 0 is the side output.  Returns (prob fp32
+    [images,Ho,Wo] = sigmoid(d1), d1 or None) with d1 the bits of upsample_bilinear(side, size)[..., 0], which is not built."""
+    side = _nhwc(side, "matte_side: side")
+    n, h, w, stride = side.shape
+    Ho, Wo = (int(v) for v in size)
+    if not (h <= Ho <= MATTE_MAX_SIDE and w <= Wo <= MATTE_MAX_SIDE) or n * Ho * Wo >= 2 ** 31:
+        raise L.M324Error(f"matte_side: the output must be no smaller than the side map {(h, w)}, within {MATTE_MAX_SIDE} a side, and images * Ho * Wo "
+                          f"below 2^31, got {(n, Ho, Wo)}")
+    prob = torch.empty((n, Ho, Wo), dtype=torch.float32, device=side.device)
+    logit = torch.empty((n, Ho, Wo), dtype=torch.float32, device=side.device) if want_logits else None
+    _launch("m324_matte_side", _p(side), h, w, stride, n, Ho, Wo, _p(prob), _p(logit))
+    _wrote(prob, logit)
+    return prob, logit
 
 
 def matte_fuse(sides, weights, bias: float, size, *, want_logits: bool = False):

@@ -27,8 +27,13 @@ def half(n):
 
 
 def stage_layout(variant, size, frames):
-    """{stage: (multiply-adds per frame, {tile width: layers})} from the layer table: stage k works at size / 2^(k-1) (rounded up), a
-    block's layers at its own pyramid of resolutions"""
+    """{stage: (multiply-adds per frame, {tile width: layers})} of a U2-Net variant at input size `size`"""
+    return table_layout(M.VARIANTS[variant], size, frames)
+
+
+def table_layout(stages, size, frames):
+    """{stage: (multiply-adds per frame, {tile width: layers})} from a stage table whose stage1 works at `size`: stage k works at
+    size / 2^(k-1) (rounded up), a block's layers at its own pyramid of resolutions"""
     out, side = {}, size
     sizes = {}
     for k in range(1, 7):
@@ -36,7 +41,7 @@ def stage_layout(variant, size, frames):
         if k < 6:
             sizes[f"stage{k}d"] = side
         side = half(side)
-    for stage, spec in M.VARIANTS[variant].items():
+    for stage, spec in stages.items():
         kind, r = spec[0], sizes[stage]
         macs, tiles = 0, {}
         for name, cin, cout, _ in M.stage_layers(*spec):
