@@ -784,6 +784,60 @@ int m324_matte_side(const float* side, int side_h, int side_w, int side_stride, 
                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Video metric, FVD (csrc/conv3d.hip; added at ABI 23 without a bump): the pieces of an I3D trunk (Inception-v1 inflated to 3D)
+ * from decoded frames to the 400 logits.  replaces: the detector call of the reference's evaluation/fvd/styleganv/fvd.py
+ * (a TorchScript I3D on the framework's convolutions) and its preprocess_single.  All tensors fp32 NDHWC.
+ *
+ * Geometry shared by m324_conv3d and m324_maxpool3d: input [samples, T, H, W, .], a window (kt, kh, kw), per-axis strides (st, sh,
+ *   sw) each 1 or 2, and an explicit FRONT padding (pt, ph, pw), 0 <= p < k.  The output is [samples, ceil(T / st), ceil(H / sh),
+ *   ceil(W / sw), .]; output (t, h, w) reads the input voxels (t st - pt + dt, h sh - ph + dh, w sw - pw + dw), 0 <= d < k.  The
+ *   TensorFlow "SAME" rule is the caller's: total = max(k - s, 0) if n % s == 0 else max(k - n % s, 0), front = total / 2.
+ *   samples * T * H * W stays below 2^31.
+ * m324_conv3d: out[v, n] = act(bias[n] + sum over taps and channels c of a[voxel(v, tap), c] * wp[tap Cin + c][n]); a voxel outside
+ *   the volume contributes 0.  The tap box is (1,1,1), (3,3,3) or (7,7,7), given by its side `box`; tap = (dt box + dh) box + dw.
+ *   a is a channel slice: channel c of voxel v at a[v lda + c], Cin % 4 = 0, lda % 4 = 0, lda >= Cin; out likewise with ldo and
+ *   Cout, Cout % 8 = 0: channels outside [0, Cout) of the ldo-wide rows are not written.  wp [Kpad, Cout] dense, Kpad = box^3 Cin
+ *   rounded up to M324_CONV_KPAD, the rows behind box^3 Cin read and zero.  A 3-channel input is a 4-channel one with zero
+ *   weights for the fourth (m324_fvd_prepare writes that input).
+ *   Arithmetic: m324_conv3x3's -- chains of M324_CONV_RUN consecutive k from 0.0f on v_mfma_f32_32x32x2_f32, one rounding per
+ *   product, the chains added in order from 0, then + bias, then max(., 0) when relu.  The same sequence for an output whatever
+ *   its place in tile, grid or batch and whatever the tile: `tile` 0 lets the library choose (m324_conv3d_tile, host only, returns
+ *   that choice for an output voxel count), 32, 64 or 128 force a width, and the bits are the same.  Consequence: the output of
+ *   stride 2 along an axis equals every second voxel along it of the stride-1 output with the same front padding.
+ * m324_maxpool3d: windows (1,3,3), (3,3,3) and (2,2,2); the maximum runs over the window's voxels INSIDE the volume: padding is
+ *   excluded (the original model's semantics; it equals the zero-padded pool of the PyTorch ports wherever the pooled map is
+ *   non-negative, as every map the network pools is, behind a ReLU).  in dense [.., C], C % 4 = 0; out a channel slice (ldo).  Exact.
+ * m324_i3d_head: x [samples, T, hw, hw, C] dense, T >= 2 -> out [samples, classes]:
+ *     pooled[n, t, c] = (((0 + x[n, t, 0, 0, c]) + x[n, t, 0, 1, c]) + ... over (dt in {0, 1}, h, w), dt slowest) / (2 hw hw),
+ *       t in 0..T - 2 (pooled: scratch of samples * (T - 1) * C floats);
+ *     logit[n, t, j] = ((q0 + q1) + (q2 + q3)), q_r the fma chain from 0.0f over the channels c = r mod 4 in order of
+ *       pooled[n, t, c] * w[c, j], w [C, classes];
+ *     out[n, j] = (sum over t in order from 0 of (logit[n, t, j] + b[j])) / (T - 1).
+ *   Nothing else is contracted; no atomics: a sample's result does not depend on the batch.
+ * m324_fvd_prepare: src [frames, H, W, 3], uint8 (M324_FVD_U8, u = (float)v / 255.0f) or fp32 in [0, 1] (M324_FVD_F32, u = v), dense
+ *   -> dst fp32 [frames, Ho, Wo, 4].  Pixel (y, x) of dst is pixel (y + y0, x + x0) of the bilinear resize of the frame to Hr x Wr
+ *   (align_corners = false, no antialiasing; per axis and in combination the rule and order of m324_upsample_bilinear, on u),
+ *   then (r - 0.5f) * 2.0f, nothing contracted; channel 3 is 0.  Hr = H and Wr = W copy u exactly.  The reference's
+ *   preprocess_single is the call with the shorter side scaled to 224, the longer to ceil, and the centre 224 x 224 crop
+ *   (ops.fvd_geometry computes it).
+ * Every entry point validates its arguments before its first HIP call and then returns M324_ERR_INVALID with a message.
+ * ------------------------------------------------------------------------------------------ */
+#define M324_CONV3D_MAX_STRIDE 16384
+#define M324_I3D_HEAD_MAX_SAMPLES 65536
+#define M324_I3D_HEAD_MAX_SIDE 64
+#define M324_FVD_U8 0
+#define M324_FVD_F32 1
+int m324_conv3d(const float* a, long lda, const float* wp, const float* bias, float* out, long ldo, int samples, int T, int H, int W, int Cin,
+                int Cout, int box, int st, int sh, int sw, int pt, int ph, int pw, int relu, int tile, void* stream);
+int m324_conv3d_tile(long voxels, int Cout);
+int m324_maxpool3d(const float* in, float* out, long ldo, int samples, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw,
+                   int pt, int ph, int pw, void* stream);
+int m324_i3d_head(const float* x, const float* w, const float* b, float* pooled, float* out, int samples, int T, int hw, int C, int classes,
+                  void* stream);
+int m324_fvd_prepare(const void* src, int mode, long frames, int H, int W, int Hr, int Wr, int y0, int x0, int Ho, int Wo, float* dst,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one
  * topology into a bit grid, the orthographic fill of such a grid, and the popcounts of two grids.  replaces: compute_iou_voxel
  * of the reference's evaluation/evaluation_pcd.py:612-637 (trimesh's subdivision voxeliser on the CPU; the reference keeps the call

@@ -134,6 +134,11 @@ SIGNATURES = {
     "m324_conv3x3_s2": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "m324_matte_prepare_ex": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "m324_matte_side": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "m324_conv3d": [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "m324_conv3d_tile": [_L, _I],
+    "m324_maxpool3d": [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "m324_i3d_head": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "m324_fvd_prepare": [_P, _I, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "m324_transpose": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_colsum": [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "m324_colsum_multi": [C.POINTER(ColsumItem), _I, _P],

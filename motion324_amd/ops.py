@@ -1704,8 +1704,215 @@ def maxpool2x2_ceil(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
     return out
 
 
+# ------------------------------------------------------------------------------------------------ 3D convolution (video metric)
+# the pieces of the I3D trunk behind FVD (csrc/conv3d.hip): fp32 NDHWC, channel slices in and out
+CONV3D_BOXES = (1, 3, 7)        # side of the tap boxes m324_conv3d has instances of
+CONV3D_MAX_STRIDE = 16384       # M324_CONV3D_MAX_STRIDE: the widest tensor a channel slice may be cut from
+POOL3D_WINDOWS = ((1, 3, 3), (3, 3, 3), (2, 2, 2))
+I3D_HEAD_MAX_SAMPLES = 65536    # M324_I3D_HEAD_MAX_SAMPLES
+I3D_HEAD_MAX_SIDE = 64          # M324_I3D_HEAD_MAX_SIDE
+FVD_MODES = {torch.uint8: 0, torch.float32: 1}         # M324_FVD_U8, M324_FVD_F32
+
+
+def same_padding(n: int, k: int, s: int):
+    """TensorFlow's "SAME" rule along one axis of n samples, window k, stride s: (front padding, output size).  The one place
+    the rule lives: the kernels take the front padding as an argument and derive the output size ceil(n / s) themselves."""
+    n, k, s = int(n), int(k), int(s)
+    if n < 1 or k < 1 or s < 1:
+        raise L.M324Error(f"same_padding: n, k and s must be at least 1, got {n}, {k}, {s}")
+    total = max(k - s, 0) if n % s == 0 else max(k - n % s, 0)
+    return total // 2, -(-n // s)
+
+
+def conv3d_kpad(cin: int, box: int) -> int:
+    """rows of the K-major weight matrix m324_conv3d reads for `cin` input channels and a tap box of side `box`"""
+    return (int(box) ** 3 * int(cin) + CONV_KPAD - 1) // CONV_KPAD * CONV_KPAD
+
+
+def pack_conv3d_weight(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, k, k, k] (torch's layout) -> fp32 [Kpad, Cout] with row ((dt k + dh) k + dw) * Cin4 + c, Cin4 = Cin rounded up
+    to a multiple of 4 (zero rows for the pad channels: the stem's three channels become four) and zero rows up to Kpad."""
+    if w.dim() != 5 or w.shape[2] not in CONV3D_BOXES or not (w.shape[2] == w.shape[3] == w.shape[4]):
+        raise L.M324Error(f"pack_conv3d_weight: expected [Cout,Cin,k,k,k] with k in {CONV3D_BOXES}, got {tuple(w.shape)}")
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    cin4 = (cin + 3) // 4 * 4
+    packed = torch.zeros((conv3d_kpad(cin4, k), cout), dtype=torch.float32)
+    taps = torch.zeros((k ** 3, cin4, cout), dtype=torch.float32)
+    taps[:, :cin] = w.detach().to(torch.float32).permute(2, 3, 4, 1, 0).reshape(k ** 3, cin, cout)
+    packed[:k ** 3 * cin4] = taps.reshape(k ** 3 * cin4, cout)
+    return packed
+
+
+def _ndhwc(x, name: str, sliced: bool) -> int:
+    """Checks fp32 NDHWC [samples,T,H,W,C] on the device, C % 4 = 0, 16-byte aligned; dense, or (sliced) a channel slice of a
+    dense tensor: returns the channel stride"""
+    _on_device(x, name)
+    if x.dtype != torch.float32 or x.dim() != 5 or 0 in x.shape or x.shape[4] % 4 or x.shape[4] > CONV_MAX_CHANNELS:
+        raise L.M324Error(f"{name}: expected fp32 NDHWC [samples,T,H,W,C] with C a multiple of 4 up to {CONV_MAX_CHANNELS}, got {x.dtype} {tuple(x.shape)}")
+    n, T, H, W, c = x.shape
+    if n * T * H * W >= 2 ** 31:
+        raise L.M324Error(f"{name}: samples * T * H * W must stay below 2^31, got {tuple(x.shape)}")
+    ld = _channel_stride(x)
+    dense = (T * H * W * ld, H * W * ld, W * ld, ld, 1)
+    if any(x.shape[i] > 1 and x.stride(i) != dense[i] for i in range(5)) or ld < c or ld % 4 or ld > CONV3D_MAX_STRIDE or (not sliced and ld != c):
+        raise L.M324Error(f"{name}: expected a dense NDHWC tensor" + (" or a channel slice of one (channel stride a multiple of 4 up to "
+                          f"{CONV3D_MAX_STRIDE})" if sliced else "") + f", got shape {tuple(x.shape)} strides {x.stride()}")
+    if x.data_ptr() % 16:
+        raise L.M324Error(f"{name}: must be 16-byte aligned (a slice starts at a channel that is a multiple of 4)")
+    return ld
+
+
+def _channel_stride(x) -> int:
+    """channel stride of an NDHWC tensor: from the stride of the innermost axis longer than 1 (-1 when that is no whole number of
+    voxels), the width when there is one voxel"""
+    for i in (3, 2, 1, 0):
+        if x.shape[i] > 1:
+            q, r = divmod(x.stride(i), math.prod(x.shape[i + 1:4]))
+            return q if r == 0 else -1
+    return x.shape[4]
+
+
+def _triple(v, name: str):
+    v = tuple(int(a) for a in ((v,) * 3 if isinstance(v, int) else v))
+    if len(v) != 3:
+        raise L.M324Error(f"{name}: expected three values (t, h, w), got {v}")
+    return v
+
+
+def _geometry3d(shape, window, stride, padding, name: str):
+    """(strides, front padding, output sizes) of a window over [T,H,W]; padding None is the SAME rule"""
+    stride = _triple(stride, f"{name}: stride")
+    if any(s not in (1, 2) for s in stride):
+        raise L.M324Error(f"{name}: every stride is 1 or 2, got {stride}")
+    same = tuple(same_padding(n, k, s) for n, k, s in zip(shape, window, stride))
+    padding = tuple(f for f, _ in same) if padding is None else _triple(padding, f"{name}: padding")
+    if any(not 0 <= p < k for p, k in zip(padding, window)):
+        raise L.M324Error(f"{name}: the front padding must be in 0..k - 1 per axis, got {padding} for the window {tuple(window)}")
+    return stride, padding, tuple(o for _, o in same)
+
+
+def _out_slice(out, shape, device, name: str):
+    """(out, channel stride): a new dense tensor, or the caller's dense tensor or channel slice of that shape"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device), shape[4]
+    if not _is_device(out) or out.device != device or tuple(out.shape) != tuple(shape):
+        raise L.M324Error(f"{name}: out must be an fp32 device tensor {tuple(shape)} (dense, or a channel slice of a dense tensor)")
+    _ndhwc(out, f"{name}: out", True)
+    return out, _channel_stride(out)
+
+
+def conv3d_tile(voxels: int, cout: int) -> int:
+    """output channels per workgroup tile (128, 64 or 32) m324_conv3d takes for this many output voxels: host-only, never in the bits"""
+    n = int(L.load().m324_conv3d_tile(int(voxels), int(cout)))
+    L.check(0 if n > 0 else n, "m324_conv3d_tile")
+    return n
+
+
+def conv3d(x: torch.Tensor, wp: torch.Tensor, bias: torch.Tensor, *, box: int, stride=(1, 1, 1), padding=None, relu: bool = True,
+           out: Optional[torch.Tensor] = None, tile: int = 0) -> torch.Tensor:
+    """3D convolution with a (box, box, box) tap box, box in 1, 3, 7, per-axis strides 1 or 2, bias and (relu) max(., 0)
+    (m324_conv3d, fp32 MFMA).  x fp32 NDHWC [samples,T,H,W,Cin], dense or a channel slice of a dense tensor, Cin % 4 = 0; wp fp32
+    [conv3d_kpad(Cin, box), Cout] (pack_conv3d_weight makes it); bias [Cout], Cout % 8 = 0.  padding: the front padding (pt, ph, pw),
+    None for the SAME rule (same_padding); voxels outside the volume read as zero.  out: None, or a tensor [samples,To,Ho,Wo,Cout]
+    that may be a channel slice of a wider dense tensor, whose other channels are left alone.  tile: 0 lets the library choose,
+    32 / 64 / 128 force a tile width; the bits are the same.  Returns out, [samples,ceil(T/st),ceil(H/sh),ceil(W/sw),Cout]."""
+    if int(box) not in CONV3D_BOXES:
+        raise L.M324Error(f"conv3d: the tap box is (1,1,1), (3,3,3) or (7,7,7), got side {box}")
+    box = int(box)
+    lda = _ndhwc(x, "conv3d: x", True)
+    n, T, H, W, cin = x.shape
+    wp = _device_array(wp, torch.float32, "conv3d: wp")
+    bias = _device_array(bias, torch.float32, "conv3d: bias")
+    if wp.dim() != 2 or wp.shape[0] != conv3d_kpad(cin, box):
+        raise L.M324Error(f"conv3d: wp must be [{conv3d_kpad(cin, box)},Cout] for Cin {cin} and box {box}, got {tuple(wp.shape)}")
+    cout = wp.shape[1]
+    if cout % 8 or not 8 <= cout <= CONV_MAX_CHANNELS or tuple(bias.shape) != (cout,):
+        raise L.M324Error(f"conv3d: Cout must be a multiple of 8 up to {CONV_MAX_CHANNELS} with bias [Cout], got wp {tuple(wp.shape)}, bias {tuple(bias.shape)}")
+    if int(tile) not in (0, 32, 64, 128):
+        raise L.M324Error(f"conv3d: tile is 0, 32, 64 or 128, got {tile}")
+    stride, padding, (To, Ho, Wo) = _geometry3d((T, H, W), (box,) * 3, stride, padding, "conv3d")
+    out, ldo = _out_slice(out, (n, To, Ho, Wo, cout), x.device, "conv3d")
+    _launch("m324_conv3d", _p(x), lda, _p(wp), _p(bias), _p(out), ldo, n, T, H, W, cin, cout, box, *stride, *padding, 1 if relu else 0, int(tile))
+    _wrote(out)
+    return out
+
+
+def maxpool3d(x: torch.Tensor, window, stride, padding=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3D max-pool with the window (1,3,3), (3,3,3) or (2,2,2) and per-axis strides 1 or 2 (m324_maxpool3d).  Padding (None: the
+    SAME rule) is excluded from the maximum.  x dense fp32 NDHWC, C % 4 = 0; out as for conv3d.  Exact."""
+    window = _triple(window, "maxpool3d: window")
+    if window not in POOL3D_WINDOWS:
+        raise L.M324Error(f"maxpool3d: the window is (1,3,3), (3,3,3) or (2,2,2), got {window}")
+    _ndhwc(x, "maxpool3d: x", False)
+    n, T, H, W, c = x.shape
+    stride, padding, (To, Ho, Wo) = _geometry3d((T, H, W), window, stride, padding, "maxpool3d")
+    out, ldo = _out_slice(out, (n, To, Ho, Wo, c), x.device, "maxpool3d")
+    _launch("m324_maxpool3d", _p(x), _p(out), ldo, n, T, H, W, c, *window, *stride, *padding)
+    _wrote(out)
+    return out
+
+
+def i3d_head(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The head of I3D (m324_i3d_head): x dense fp32 [samples,T,hw,hw,C], T >= 2; the average over a (2, hw, hw) window with stride
+    1 in time, the 1 x 1 x 1 logits layer w fp32 [C,classes] with bias b [classes], and the mean over the T - 1 time steps.
+    Returns fp32 [samples,classes].  A fixed order of sums (include/m324.h): deterministic, independent of the batch."""
+    _ndhwc(x, "i3d_head: x", False)
+    n, T, hh, hw, c = x.shape
+    if hh != hw or not 2 <= T <= I3D_HEAD_MAX_SIDE or hw > I3D_HEAD_MAX_SIDE or n > I3D_HEAD_MAX_SAMPLES:
+        raise L.M324Error(f"i3d_head: expected [samples,T,hw,hw,C] with T in 2..{I3D_HEAD_MAX_SIDE}, hw up to {I3D_HEAD_MAX_SIDE} and at most "
+                          f"{I3D_HEAD_MAX_SAMPLES} samples, got {tuple(x.shape)}")
+    w = _device_array(w, torch.float32, "i3d_head: w")
+    b = _device_array(b, torch.float32, "i3d_head: b")
+    if w.dim() != 2 or w.shape[0] != c or not 1 <= w.shape[1] <= CONV_MAX_CHANNELS or tuple(b.shape) != (w.shape[1],):
+        raise L.M324Error(f"i3d_head: w must be [{c},classes] with classes up to {CONV_MAX_CHANNELS} and b [classes], got {tuple(w.shape)}, {tuple(b.shape)}")
+    classes = w.shape[1]
+    if out is None:
+        out = torch.empty((n, classes), dtype=torch.float32, device=x.device)
+    elif not _is_device(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, classes) or not out.is_contiguous() or out.device != x.device:
+        raise L.M324Error(f"i3d_head: out must be a contiguous fp32 device tensor {(n, classes)}")
+    pooled = torch.empty((n * (T - 1) * c,), dtype=torch.float32, device=x.device)
+    _launch("m324_i3d_head", _p(x), _p(w), _p(b), _p(pooled), _p(out), n, T, hw, c, classes)
+    _wrote(out)
+    return out
+
+
+def fvd_geometry(H: int, W: int, resolution: Optional[int] = 224):
+    """(Hr, Wr, y0, x0, Ho, Wo) of the reference's preprocess_single: the shorter side scaled to `resolution`, the longer to
+    ceil(side * resolution / shorter), and the centre resolution x resolution crop.  resolution None: the frame as it is."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or (resolution is not None and int(resolution) < 1):
+        raise L.M324Error(f"fvd_geometry: sizes must be at least 1, got {H} x {W} -> {resolution}")
+    if resolution is None:
+        return H, W, 0, 0, H, W
+    r = int(resolution)
+    scale = r / min(H, W)
+    Hr, Wr = (r, math.ceil(W * scale)) if H < W else (math.ceil(H * scale), r)
+    return Hr, Wr, (Hr - r) // 2, (Wr - r) // 2, r, r
+
+
+def fvd_prepare(src: torch.Tensor, resolution: Optional[int] = 224, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The trunk's input fp32 NDHWC [samples,T,res,res,4] (channel 3 is zero) from clips uint8 [samples,T,H,W,3] or fp32 in [0, 1]
+    of that shape (m324_fvd_prepare): bilinear resize (align_corners=False, no antialiasing) of the shorter side to `resolution`,
+    centre crop, (v - 0.5) * 2.  resolution None keeps the frames' own size."""
+    _on_device(src, "fvd_prepare")
+    if src.dtype not in FVD_MODES or src.dim() != 5 or src.shape[4] != 3 or 0 in src.shape:
+        raise L.M324Error(f"fvd_prepare: expected uint8 or fp32 [samples,T,H,W,3], got {src.dtype} {tuple(src.shape)}")
+    n, T, H, W = src.shape[:4]
+    Hr, Wr, y0, x0, Ho, Wo = fvd_geometry(H, W, resolution)
+    if max(H, W, Hr, Wr) > MATTE_MAX_SIDE or n * T * H * W >= 2 ** 31 or n * T * Ho * Wo >= 2 ** 31:
+        raise L.M324Error(f"fvd_prepare: sizes up to {MATTE_MAX_SIDE} and samples * T * H * W below 2^31, got {tuple(src.shape)} -> {Hr} x {Wr}")
+    src = src.detach().contiguous()
+    if out is None:
+        out = torch.empty((n, T, Ho, Wo, 4), dtype=torch.float32, device=src.device)
+    elif not _is_device(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, T, Ho, Wo, 4) or not out.is_contiguous() or out.device != src.device:
+        raise L.M324Error(f"fvd_prepare: out must be a contiguous fp32 device tensor {(n, T, Ho, Wo, 4)}")
+    _launch("m324_fvd_prepare", _p(src), FVD_MODES[src.dtype], n * T, H, W, Hr, Wr, y0, x0, Ho, Wo, _p(out))
+    _wrote(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ perceptual evaluation
-LPIPS_MAX_CHANNELS = 1024       # M324_LPIPS_MAX_CHANNELS
+LPIPS_MAX_CHANNELS = 1024      # M324_LPIPS_MAX_CHANNELS
 LPIPS_CHUNKS = 64               # M324_LPIPS_CHUNKS
 LPIPS_MODES = {"u8_nhwc": 0, "f32_nchw": 1}
 
