@@ -795,3 +795,11 @@ def merge_parts(parts, lses, out_dtype=torch.bfloat16):
     val = sum(tok(wi / tot) * p for wi, p in zip(w, parts))
     mag = sum(tok(wi / tot) * p.abs() for wi, p in zip(w, parts))
     return val, _round_out(val, drel * mag, out_dtype)
+
+
+def gemm_tn(x, y, slices):
+    """m324_gemm_tn + m324_colsum (the weight gradient dW[n, j] = sum_m x[m, n] y[m, j], bf16 operands [M, N] and [M, Kc], `slices`
+    token ranges): the products of two bf16 values are exact in fp32, so what is left is the sum of M exact terms -- inside a slice in
+    the MFMA's own order (the factor 2 of this file), the slices - 1 additions of m324_colsum behind it: 2 (M + slices) U32 |x|^T |y|."""
+    x, y = _f64(x), _f64(y)
+    return 2 * (x.shape[0] + slices) * U32 * (x.abs().T @ y.abs())

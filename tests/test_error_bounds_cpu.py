@@ -17,6 +17,7 @@ import torch
 import error_bounds as eb
 import optimizer_cases as oc
 import rowkernel_cases as rc
+import wgrad_cases as wc
 from conftest import rel_err
 
 BF = torch.bfloat16
@@ -872,3 +873,47 @@ def test_merge_parts_bound_is_sound_and_rejects_a_part_weighted_as_its_neighbour
             inv = 1.0 / sum(w)
             bad = sum(tok(wi * inv) * p for wi, p in zip(w, parts)).to(dt).float()
             assert float(eb.violations(bad, ref, bound).double().mean()) > 0.95
+
+
+# ------------------------------------------------------------------------------------------- the weight-gradient GEMM (m324_gemm_tn)
+def _tn_emulation(x, y, lengths, order):
+    """fp32 per-slice sums of the exact products, then the slices added one after the other in fp32.  order 0: one fp32 matrix
+    product per slice; order 1: 32-token pieces from the back of the slice to its front, added one by one"""
+    xf, yf = x.float(), y.float()
+    total, m = None, 0
+    for n in lengths:
+        xs, ys = xf[m:m + n], yf[m:m + n]
+        if order == 0:
+            part = xs.T @ ys
+        else:
+            part = torch.zeros((x.shape[1], y.shape[1]))
+            for b in range((n - 1) // 32 * 32, -1, -32):
+                part = part + xs[b:b + 32].T @ ys[b:b + 32]
+        total = part if total is None else total + part
+        m += n
+    return total
+
+
+@pytest.mark.parametrize("c", wc.TN_CASES, ids=[wc.case_id(c) for c in wc.TN_CASES])
+def test_gemm_tn_bound_is_sound(c):
+    x, y = wc.gaussian_operands(c.M, c.N, c.Kc, 141)
+    used, _, lengths = wc.slice_plan(c.M, c.slices)
+    ref, bound = x.double().T @ y.double(), eb.gemm_tn(x, y, used)
+    for order in (0, 1):
+        eb.assert_within(_tn_emulation(x, y, lengths, order), ref, bound, f"gemm_tn emulation {wc.case_id(c)} order {order}")
+
+
+@pytest.mark.parametrize("M,N,Kc,slices", [(63, 136, 72, 1), (200, 192, 328, 4), (1000, 136, 72, 5), (1024, 256, 256, 4)])
+def test_gemm_tn_bound_rejects_a_dropped_token(M, N, Kc, slices):
+    """Operands of magnitude 0.5 .. 1: a token left out of the contraction takes x[m, n] y[m, j], at least 0.25, out of EVERY element,
+    and the bound is at most 2 (1024 + 5) 2^-24 1024 < 0.126 for M <= 1024 -- so every element is flagged, by the numbers alone."""
+    x, y = wc.away_from_zero(M, N, 142), wc.away_from_zero(M, Kc, 143)
+    used, ks, lengths = wc.slice_plan(M, slices)
+    ref, bound = x.double().T @ y.double(), eb.gemm_tn(x, y, used)
+    assert float(bound.max()) < 0.126 and float(x.float().abs().min() * y.float().abs().min()) >= 0.25
+    eb.assert_within(_tn_emulation(x, y, lengths, 0), ref, bound, "unfaulted")
+    for m in (0, ks - 1 if used > 1 else M // 2, M - 1):          # the first token, the last of the first slice, the last of all
+        keep = torch.ones(M, dtype=torch.bool)
+        keep[m] = False
+        out = _tn_emulation(x[keep], y[keep], [n - (1 if sum(lengths[:i]) <= m < sum(lengths[:i + 1]) else 0) for i, n in enumerate(lengths)], 0)
+        assert bool(eb.violations(out, ref, bound).all()), (M, N, Kc, m)
