@@ -456,7 +456,8 @@ def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, 
             qkv_heads: Optional[tuple] = None):
     """out = epilogue(a @ w^T) on MX operands (m324_gemm_mx).  Epilogues: `out` bf16 [M, N] (+ bias); qkv_heads, a QKVHeads
     (`out` None); `out` the fp32 residual stream with residual=out (+ bias, * gamma); `out` an MX operand [M, N] (+ bias, GELU
-    with act=ACT_GELU).  Returns `out` (the first head-major output for qkv_heads)."""
+    with act=ACT_GELU).  Any other combination raises M324Error: none of bias / act / gamma / residual is ever dropped.
+    Returns `out` (the first head-major output for qkv_heads)."""
     M, K = a.q.shape[0], a.q.shape[1]
     N = w.q.shape[0]
     pa, la, psa, lsa = _mx_rows(a, M, K, "a")
@@ -470,6 +471,11 @@ def gemm_mx(a: MX, w: MX, out, *, bias=None, act: int = L.ACT_NONE, gamma=None, 
     args.gamma = _vec(gamma, N, "gamma")
     pcs, lcs = None, 0
     first = out
+    # the branches below read residual only for a plain tensor `out`: refuse it elsewhere instead of dropping it (act / gamma
+    # with the q|k|v heads, and every other combination that is not built, are refused by m324_gemm_mx itself)
+    if residual is not None and (qkv_heads is not None or isinstance(out, MX)):
+        raise L.M324Error("gemm_mx: residual= goes with the fp32 residual stream only (residual=out), not with "
+                          + ("qkv_heads=" if qkv_heads is not None else "an MX output"))
     if qkv_heads is not None:
         first = _qkv_heads_args(args, qkv_heads, M, N, "gemm_mx")
     elif isinstance(out, MX):

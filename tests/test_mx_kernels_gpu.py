@@ -1,5 +1,7 @@
 """Block-scaled FP8 (MX) kernels: m324_mx_quant against a numpy statement of the quantisation rule (include/m324.h, "MX
-operands"), m324_gemm_mx against fp64 products of the dequantised operands, m324_layernorm_mx against m324_layernorm + the rule."""
+operands"), m324_gemm_mx against fp64 products of the dequantised operands, m324_layernorm_mx against m324_layernorm + the rule
+and against fp64 LayerNorm within its error bound.  The reference, the operand builders and the checker (admissible sets) live
+in tests/mx_cases.py; their names stay importable from here (tests/test_strides_gpu.py)."""
 import math
 
 import numpy as np
@@ -7,6 +9,8 @@ import pytest
 import torch
 
 import error_bounds
+import mx_cases
+from mx_cases import E4M3, _e4m3_table, _int_operands, _mx_to_np, _quant_input, _rand_mx, _rne_e4m3, _to_mx, deq, mx_quant_ref  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -18,93 +22,7 @@ def _ops():
     return ops
 
 
-# ---------------------------------------------------------------------------------------------------- numpy reference
-def _e4m3_table():
-    """value of every finite e4m3fn code 0x00 .. 0x7E (positive half)"""
-    v = np.zeros(127)
-    for c in range(127):
-        e, m = c >> 3, c & 7
-        v[c] = m * 2.0 ** -9 if e == 0 else (1 + m / 8) * 2.0 ** (e - 7)
-    return v
-
-
-E4M3 = _e4m3_table()
-
-
-def _rne_e4m3(y):
-    """|y| <= 448 -> e4m3fn code, round to nearest, ties to the even code (independent of the kernels: table search)"""
-    a = np.abs(y)
-    hi = np.searchsorted(E4M3, a, side="left").clip(0, 126)
-    lo = (hi - 1).clip(0, 126)
-    dl, dh = a - E4M3[lo], E4M3[hi] - a
-    code = np.where(dl < dh, lo, np.where(dh < dl, hi, np.where(lo % 2 == 0, lo, hi)))
-    code = np.where(a == E4M3[hi], hi, code)
-    return (code | np.where(np.signbit(y), 0x80, 0)).astype(np.uint8)
-
-
-def mx_quant_ref(x):
-    """x float64-representable [rows, K] -> (q uint8, s uint8) by the rule: X = ceil(log2(amax / 448)) in [-127, 127]"""
-    rows, K = x.shape
-    b = x.reshape(rows, K // 32, 32).astype(np.float64)
-    q = np.zeros(b.shape, np.uint8)
-    s = np.zeros(b.shape[:2], np.uint8)
-    for r in range(rows):
-        for j in range(K // 32):
-            v = b[r, j]
-            if not np.all(np.isfinite(v)):
-                s[r, j], q[r, j] = 0xFF, 0x7F
-                continue
-            amax = np.abs(v).max()
-            if amax == 0:
-                continue
-            X = math.ceil(math.log2(amax / 448.0))
-            while amax > 448.0 * 2.0 ** X:          # guard against log2 rounding: the smallest X with amax <= 448 2^X
-                X += 1
-            while amax <= 448.0 * 2.0 ** (X - 1):
-                X -= 1
-            X = max(-127, min(127, X))
-            s[r, j] = X + 127
-            q[r, j] = _rne_e4m3(v * 2.0 ** -X)
-    return q.reshape(rows, K), s
-
-
-def deq(q, s):
-    """(q, s) -> float64 values"""
-    q = np.asarray(q, np.uint8)
-    mag = np.where((q & 0x7F) == 0x7F, np.nan, E4M3[np.minimum(q & 0x7F, 126)])
-    v = np.where(q & 0x80, -mag, mag)
-    sc = np.where(s == 0xFF, np.nan, 2.0 ** (s.astype(np.float64) - 127))
-    return v * np.repeat(sc, 32, axis=1)
-
-
-def _mx_to_np(m, rows, K):
-    return m.q[:rows, :K].cpu().numpy(), m.s[:rows, :K // 32].cpu().numpy()
-
-
-def _to_mx(q, s):
-    from motion324_amd.ops import mx_empty
-    rows, K = q.shape
-    m = mx_empty(rows, K, DEV)
-    m.q.copy_(torch.from_numpy(np.ascontiguousarray(q)))
-    m.s.copy_(torch.from_numpy(np.ascontiguousarray(s)))
-    return m
-
-
 # ---------------------------------------------------------------------------------------------------- quantiser
-def _quant_input():
-    rng = np.random.default_rng(7)
-    rows, K = 96, 256
-    x = (rng.standard_normal((rows, K)) * 2.0 ** rng.integers(-20, 21, (rows, 1))).astype(np.float32)
-    x[3, 32:64] = 0.0                                            # zero block
-    x[4, :32] = 2.0 ** rng.integers(-30, 30, 32)                 # exact powers of two
-    for i, a in enumerate((448.0, 449.0, 447.99997, 512.0, 896.0, 896.0001, 224.0, 3.0e38, 1e-38, 1e-42)):
-        x[5 + i, 64:96] = rng.uniform(-1, 1, 32).astype(np.float32) * np.float32(a) / 2
-        x[5 + i, 64] = np.float32(a)                             # amax next to / on a scale boundary
-    x[20, 0:32] = np.linspace(-448, 448, 32, dtype=np.float32) / 64    # element rounding ties
-    x[21, 5], x[22, 40], x[23, 100] = np.nan, np.inf, -np.inf     # non-finite blocks
-    return x
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_mx_quant_is_bit_identical_to_the_rule(dtype):
     ops = _ops()
@@ -140,18 +58,6 @@ def test_layernorm_mx_equals_quantised_layernorm():
 
 
 # ---------------------------------------------------------------------------------------------------- GEMM
-def _int_operands(rows, K, seed, asym=False):
-    """integer-valued MX operands: elements -8 .. 8 (exact in e4m3), scales 2^-1 .. 2^1 -> every product exact in fp32"""
-    rng = np.random.default_rng(seed)
-    v = rng.integers(-8, 9, (rows, K)).astype(np.float64)
-    if asym:
-        v += (np.arange(rows)[:, None] % 5) - 2
-        v = np.clip(v, -8, 8)
-    s = (127 + rng.integers(-1, 2, (rows, K // 32))).astype(np.uint8)
-    q = _rne_e4m3(v)
-    return q, s
-
-
 @pytest.mark.parametrize("M,N,K", [(128, 128, 128), (200, 2304, 768), (333, 3072, 768), (130, 768, 3072), (64, 192, 128)])
 def test_gemm_mx_exact_on_integer_operands(M, N, K):
     ops = _ops()
@@ -181,13 +87,6 @@ def test_gemm_mx_lane_map_single_k():
     ops.gemm_mx(_to_mx(qa, sa), _to_mx(qw, sw), out, residual=out)
     ref = deq(qa, sa) @ deq(qw, sw).T
     assert np.array_equal(out.cpu().numpy(), ref.astype(np.float32))
-
-
-def _rand_mx(rows, K, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(rows, K, generator=g) * scale
-    q, s = mx_quant_ref(x.numpy())
-    return q, s
 
 
 def test_gemm_mx_residual_epilogue_matches_fp64():
@@ -297,3 +196,386 @@ def test_gemm_mx_refuses_unbuilt_problems_before_launching():
     a, w = ops.mx_empty(128, 192, DEV), ops.mx_empty(128, 192, DEV)
     with pytest.raises(M324Error, match="multiple of 128"):
         ops.gemm_mx(a, w, torch.empty(128, 128, dtype=torch.bfloat16, device=DEV))
+
+
+# ==================================================================================================== tails, scale range, epilogues
+# Everything below compares with tests/mx_cases.py: bit equality where the arithmetic is exact (the quantiser; the GEMM on
+# integer operands with power-of-two scales), assert_mx_within against fp64 where it is not (LayerNorm -> MX).
+SENT = 0xA5                                                       # fill byte of MX outputs: what is not written keeps it
+
+
+def _mx_out(rows, K):
+    """MX output storage one row and one block larger than [rows, K], filled with SENT"""
+    from motion324_amd.ops import MX
+    return MX(torch.full((rows + 1, K + 32), SENT, dtype=torch.uint8, device=DEV),
+              torch.full((rows + 1, K // 32 + 1), SENT, dtype=torch.uint8, device=DEV))
+
+
+def _mx_result(m, rows, K, what):
+    """(q, s) of the [rows, K] corner after checking that nothing outside it was written"""
+    q, s = m.q.cpu().numpy(), m.s.cpu().numpy()
+    assert np.all(q[rows:] == SENT) and np.all(q[:, K:] == SENT), (what, "element bytes written outside [rows, K]")
+    assert np.all(s[rows:] == SENT) and np.all(s[:, K // 32:] == SENT), (what, "scale bytes written outside [rows, K / 32]")
+    return q[:rows, :K], s[:rows, :K // 32]
+
+
+# ---------------------------------------------------------------------------------------------------- quantiser
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("rows,K", mx_cases.QUANT_SHAPES)
+def test_mx_quant_tails_and_special_blocks_bit_exact(rows, K, dtype):
+    """Block counts that are no multiple of the 64 blocks of a workgroup (the `g >= rows * nb` exit), nb = 1, 3, 5, 7 (a wave's
+    16 blocks straddle rows), a block of -0.0, a negative amax element and, in fp32, amax mantissas on and next to 1.75."""
+    ops = _ops()
+    x = torch.from_numpy(mx_cases.quant_input(rows, K).copy()).to(dtype)
+    out = _mx_out(rows, K)
+    ops.mx_quant(x.to(DEV), out)
+    q, s = _mx_result(out, rows, K, f"mx_quant {rows} x {K}")
+    qr, sr = mx_quant_ref(x.float().numpy())
+    assert np.array_equal(s, sr), np.argwhere(s != sr)[:8]
+    assert np.array_equal(q, qr), np.argwhere(q != qr)[:8]
+    zero = np.all(x.float().numpy().reshape(rows, K // 32, 32) == 0, axis=2)
+    assert np.all(s[zero] == 0) and np.all(q.reshape(rows, K // 32, 32)[zero] == 0)       # -0.0 blocks included: +0 elements
+
+
+# ---------------------------------------------------------------------------------------------------- LayerNorm -> MX
+@pytest.mark.parametrize("with_b", [True, False])
+@pytest.mark.parametrize("rows,C", mx_cases.LN_SHAPES)
+def test_layernorm_mx_within_fp64_bound(rows, C, with_b):
+    """Against fp64 LayerNorm and error_bounds.layernorm: every scale byte admissible, every element code in its range (bit
+    equality wherever the range is one code; tests/test_mx_cases_cpu.py caps the share of the others at 3 %)."""
+    ops = _ops()
+    x, w, b, ref, err = mx_cases.ln_case(rows, C, with_b)
+    out = _mx_out(rows, C)
+    ops.layernorm_mx(x.to(DEV), w.to(DEV), b.to(DEV) if with_b else None, mx_cases.LN_EPS, out)
+    what = f"layernorm_mx {rows} x {C} b={with_b}"
+    q, s = _mx_result(out, rows, C, what)
+    blocks, elements = mx_cases.assert_mx_within(q, s, ref, err, what)
+    print(f"{what}: {100 * elements:.2f} % of elements admit two codes, {100 * blocks:.2f} % of blocks two bytes")
+    assert elements <= mx_cases.CAP_ELEMENTS and blocks <= mx_cases.CAP_BLOCKS
+
+
+@pytest.mark.parametrize("with_b", [True, False])
+@pytest.mark.parametrize("rows,C", [(5, 192), (6, 800)])
+def test_layernorm_mx_constant_row_is_the_quantised_bias(rows, C, with_b):
+    """x - mean = 0 exactly on a constant row (its sums are exact: small integers), so y = b bit for bit; without b the row is
+    all-zero blocks: byte 0 and +0 elements, whatever the sign of w."""
+    ops = _ops()
+    x, w, b = mx_cases.ln_input(rows, C)
+    x[1], x[rows - 1] = 3.0, -5.0
+    m = ops.layernorm_mx(x.to(DEV), w.to(DEV), b.to(DEV) if with_b else None, mx_cases.LN_EPS)
+    q, s = _mx_to_np(m, rows, C)
+    want = b.numpy()[None, :] if with_b else np.zeros((1, C), np.float32)
+    qr, sr = mx_quant_ref(want)
+    for r in (1, rows - 1):
+        assert np.array_equal(s[r], sr[0]) and np.array_equal(q[r], qr[0]), r
+    if not with_b:
+        assert not s[1].any() and not q[1].any()
+
+
+def test_layernorm_mx_nan_row_reaches_exactly_its_row():
+    ops = _ops()
+    rows, C = 9, 288
+    x, w, b = mx_cases.ln_input(rows, C)
+    clean = ops.layernorm_mx(x.to(DEV), w.to(DEV), b.to(DEV), mx_cases.LN_EPS)
+    qc, sc = _mx_to_np(clean, rows, C)
+    x[5, 77] = float("nan")                                       # rows 4 .. 7 share a workgroup
+    m = ops.layernorm_mx(x.to(DEV), w.to(DEV), b.to(DEV), mx_cases.LN_EPS)
+    q, s = _mx_to_np(m, rows, C)
+    assert np.all(s[5] == 0xFF) and np.all(q[5] == 0x7F)
+    others = np.arange(rows) != 5
+    assert np.array_equal(s[others], sc[others]) and np.array_equal(q[others], qc[others])
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: outputs with a frame
+def _bits(t):
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()]).cpu().numpy()
+
+
+def _framed(M, N, dtype, inner=None):
+    """[M + 1, N + 8] of NaN (a spare row and spare columns that must stay) with the [M, N] corner set to `inner` (or left NaN);
+    returns (whole tensor, the view a kernel gets)"""
+    big = torch.full((M + 1, N + 8), float("nan"), dtype=dtype, device=DEV)
+    if inner is not None:
+        big[:M, :N] = torch.from_numpy(np.asarray(inner)).to(dtype).to(DEV)
+    return big, big[:M, :N]
+
+
+def _framed_result(big, M, N, what):
+    fill = _bits(torch.full((1,), float("nan"), dtype=big.dtype))[0]
+    bits = _bits(big)
+    assert np.all(bits[M:] == fill) and np.all(bits[:, N:] == fill), (what, "written outside [M, N]")
+    return big[:M, :N].float().cpu().numpy() if big.dtype == torch.bfloat16 else big[:M, :N].cpu().numpy()
+
+
+def _bf16_of(ref):
+    return torch.from_numpy(np.asarray(ref)).float().to(torch.bfloat16).float().numpy()      # exact fp32 value, rounded once
+
+
+def _run_exact(kind, qa, sa, qw, sw, what, bias=None, gamma=None, res=None):
+    """One m324_gemm_mx launch on integer operands into a framed output of `kind` ("bf16", "f32", "mx"), compared bit for bit
+    with the fp64 result rounded once to the output type: ((a w^T + bias) gamma + res; "f32" updates res, zero by default, in
+    place).  Returns (got, want) as the test may want to say more about a difference; asserts equality itself."""
+    ops = _ops()
+    M, N = qa.shape[0], qw.shape[0]
+    ref = deq(qa, sa) @ deq(qw, sw).T
+    dev = {k: None if v is None else torch.from_numpy(np.asarray(v, np.float32)).to(DEV) for k, v in (("bias", bias), ("gamma", gamma))}
+    if bias is not None:
+        ref = ref + np.asarray(bias, np.float64)
+    if kind == "mx":
+        out = _mx_out(M, N)
+        ops.gemm_mx(_to_mx(qa, sa), _to_mx(qw, sw), out, bias=dev["bias"])
+        q, s = _mx_result(out, M, N, what)
+        qr, sr = mx_quant_ref(ref)
+        assert np.array_equal(s, sr), (what, np.argwhere(s != sr)[:8])
+        assert np.array_equal(q, qr), (what, np.argwhere(q != qr)[:8])
+        return (q, s), (qr, sr)
+    if kind == "bf16":
+        big, view = _framed(M, N, torch.bfloat16)
+        ops.gemm_mx(_to_mx(qa, sa), _to_mx(qw, sw), view, bias=dev["bias"])
+        want = _bf16_of(ref)
+    else:
+        res = np.zeros((M, N)) if res is None else res
+        if gamma is not None:
+            ref = ref * np.asarray(gamma, np.float64)
+        ref = ref + res
+        big, view = _framed(M, N, torch.float32, res)
+        ops.gemm_mx(_to_mx(qa, sa), _to_mx(qw, sw), view, bias=dev["bias"], gamma=dev["gamma"], residual=view)
+        want = ref.astype(np.float32)
+        assert np.array_equal(want.astype(np.float64)[np.isfinite(ref)], ref[np.isfinite(ref)])      # the case is exact in fp32
+    got = _framed_result(big, M, N, what)
+    same = (got == want) | (np.isnan(got) & np.isnan(want))
+    assert same.all(), (what, int((~same).sum()), [(int(r), int(c), float(got[r, c]), float(want[r, c])) for r, c in np.argwhere(~same)[:8]])
+    return got, want
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: scale range
+G_WIDE = (-126, -100, -64, 0, 1, 64, 100, 126)                    # per block of K = 256: A gets 2^g, W gets 2^-g
+G_ENDS = (-127, -100, -64, 0, 1, 64, 100, 127)                    # bytes 0 and 254 on both sides
+
+
+def _scale_range_operands(g, per_block=False):
+    """M = N = 128, K = 256.  A byte 127 + g(blk) + r(row), W byte 127 - g(blk) + c(col), r and c in -1 .. 1 (0 in the blocks
+    where |g| = 127, so that the bytes there are exactly 0 and 254): every product is an integer times 2^(r + c), a multiple of
+    1/4 below 2^17, so the fp32 sum is exact in any order -- IF the scaled MFMA applies 2^(s - 127) to every byte as
+    include/m324.h states, combining 2^-126 with 2^+126 without leaving fp32's range in between.
+    With r and c per row / column alone, a kernel that takes the scales of the WRONG block for A and W alike still gets every
+    product right (g cancels); per_block draws r(row, blk) and c(col, blk), so that the pairing of scale and block matters."""
+    rng = np.random.default_rng(21)
+    M = N = 128
+    qa, qw = _rne_e4m3(rng.integers(-8, 9, (M, 256)).astype(np.float64)), _rne_e4m3(rng.integers(-8, 9, (N, 256)).astype(np.float64))
+    g = np.asarray(g)
+    free = (np.abs(g) < 127)[None, :]
+    if per_block:
+        r, c = rng.integers(-1, 2, (M, 8)) * free, rng.integers(-1, 2, (N, 8)) * free
+    else:
+        r, c = (np.arange(M) % 3 - 1)[:, None] * free, ((np.arange(N) // 2) % 3 - 1)[:, None] * free
+    sa, sw = 127 + g[None, :] + r, 127 - g[None, :] + c
+    assert sa.min() >= 0 and sw.min() >= 0 and sa.max() <= 254 and sw.max() <= 254
+    return qa, sa.astype(np.uint8), qw, sw.astype(np.uint8)
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f32"])
+@pytest.mark.parametrize("g,per_block", [(G_WIDE, False), (G_ENDS, False), (G_WIDE, True)], ids=["wide", "bytes_0_and_254", "wide_per_block"])
+def test_gemm_mx_scale_range_exact(g, per_block, kind):
+    qa, sa, qw, sw = _scale_range_operands(g, per_block)
+    if g is G_ENDS:
+        assert (sa[:, 0] == 0).all() and (sw[:, 0] == 254).all() and (sa[:, 7] == 254).all() and (sw[:, 7] == 0).all()
+    _run_exact(kind, qa, sa, qw, sw, f"scale range {g} -> {kind}")
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: shapes, tile order
+@pytest.mark.parametrize("kind", ["bf16", "f32", "mx"])
+@pytest.mark.parametrize("M,N,K,xcd", [(1, 64, 128, None), (129, 64, 256, None), (127, 192, 128, None), (300, 640, 128, 0),
+                                       (300, 640, 128, None)])
+def test_gemm_mx_small_and_ragged_shapes_exact(M, N, K, xcd, kind, tune):
+    """One row; a second row tile holding one row; N = 64 (half the waves idle); N = 192 (the last column tile half empty) with a
+    ragged M through store_tile_mx's shuffles; 15 tiles (no multiple of the 8 XCDs) in round-robin and in XCD-contiguous order."""
+    if xcd is not None:
+        tune("M324_XCD", xcd)
+    qa, sa = _int_operands(M, K, 31)
+    qw, sw = _int_operands(N, K, 32, asym=True)
+    _run_exact(kind, qa, sa, qw, sw, f"{M} x {N} x {K} -> {kind}, M324_XCD={xcd}")
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: epilogue forms
+def _epilogue_operands():
+    M, N, K = 127, 192, 128
+    rng = np.random.default_rng(41)
+    qa, sa = _int_operands(M, K, 42)
+    qw, sw = _int_operands(N, K, 43, asym=True)
+    bias = rng.integers(-16, 17, N).astype(np.float64)
+    gamma = 2.0 ** rng.integers(-2, 3, N)
+    res = rng.integers(-64, 65, (M, N)).astype(np.float64)
+    return qa, sa, qw, sw, bias, gamma, res
+
+
+@pytest.mark.parametrize("kind", ["bf16", "mx"])
+def test_gemm_mx_integer_bias_exact(kind):
+    """bf16 output with bias, and MX output with bias and no activation (bit-exact against mx_quant_ref of the fp64 result)"""
+    qa, sa, qw, sw, bias, _, _ = _epilogue_operands()
+    _run_exact(kind, qa, sa, qw, sw, f"{kind} + bias", bias=bias)
+
+
+@pytest.mark.parametrize("with_bias,with_gamma", [(True, False), (False, True), (True, True), (False, False)])
+def test_gemm_mx_residual_update_forms_exact(with_bias, with_gamma):
+    """x <- (a w^T + bias) gamma + x element by element: integer bias and residual, power-of-two gamma, every value a multiple of
+    2^-4 below 2^20"""
+    qa, sa, qw, sw, bias, gamma, res = _epilogue_operands()
+    _run_exact("f32", qa, sa, qw, sw, f"residual update bias={with_bias} gamma={with_gamma}", bias=bias if with_bias else None,
+               gamma=gamma if with_gamma else None, res=res)
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: q|k|v heads
+@pytest.mark.parametrize("parts,norm,vt", [("kv", True, False), ("q", True, False), ("qkv", False, False), ("kv", True, True)],
+                         ids=["kv_knorm", "q_alone", "qkv_no_norm", "kv_vt"])
+def test_gemm_mx_qkv_heads_parts(parts, norm, vt):
+    ops = _ops()
+    B, L, H, K = 2, 128, 2, 128
+    C = H * 64
+    M, N = B * L, len(parts) * C
+    qa, sa = _rand_mx(M, K, 51)
+    qw, sw = _rand_mx(N, K, 52, 0.1)
+    g = torch.Generator().manual_seed(53)
+    bias, qn, kn = torch.randn(N, generator=g) * 0.1, torch.rand(64, generator=g) + 0.5, torch.rand(64, generator=g) + 0.5
+    scale = 0.18
+    outs = {p: torch.full((B, H, 64, L) if (p == "v" and vt) else (B, H, L, 64), float("nan"), dtype=torch.bfloat16, device=DEV)
+            for p in parts}
+    nw = {"q": qn if norm else None, "k": kn if norm else None, "v": None}
+    ops.gemm_mx(_to_mx(qa, sa), _to_mx(qw, sw), None, bias=bias.to(DEV),
+                qkv_heads=(outs.get("q"), outs.get("k"), outs.get("v"), nw["q"].to(DEV) if "q" in parts and norm else None,
+                           nw["k"].to(DEV) if "k" in parts and norm else None, 1e-5, scale, L, H))
+    da, dw = torch.from_numpy(deq(qa, sa)), torch.from_numpy(deq(qw, sw))
+    p64 = da @ dw.T + bias.double()
+    heads = p64.reshape(B, L, len(parts), H, 64).permute(2, 0, 3, 1, 4)              # [parts, B, H, L, 64]
+    for i, p in enumerate(parts):
+        sc_ = scale if p == "q" else 1.0
+        ref = heads[i]
+        if nw[p] is not None:
+            ref = ref * torch.rsqrt((ref * ref).mean(-1, keepdim=True) + 1e-5) * nw[p].double()
+        ref = ref * sc_
+        bound = error_bounds.qkv_heads(da, dw[i * C:(i + 1) * C], bias=bias[i * C:(i + 1) * C], norm_w=nw[p], eps=1e-5, scale=sc_)
+        bound = bound.reshape(B, L, H, 64).permute(0, 2, 1, 3)
+        if p == "v" and vt:
+            from conftest import vt_layout
+            ref, bound = vt_layout(ref), vt_layout(bound)
+        error_bounds.assert_within(outs[p], ref, bound, f"{p} of parts {parts} (norm={norm}, vt={vt})")
+
+
+# ---------------------------------------------------------------------------------------------------- GEMM: non-finite operands
+def _poison(q, s, row, blk):
+    q, s = q.copy(), s.copy()
+    q[row, blk * 32:blk * 32 + 32], s[row, blk] = 0x7F, 0xFF
+    return q, s
+
+
+@pytest.mark.parametrize("kind", ["bf16", "f32"])
+def test_gemm_mx_nan_weight_block_reaches_exactly_its_column(kind):
+    qa, sa, qw, sw, bias, gamma, res = _epilogue_operands()
+    qw, sw = _poison(qw, sw, 70, 2)
+    got, _ = _run_exact(kind, qa, sa, qw, sw, f"NaN block in W row 70 -> {kind}", bias=bias, gamma=gamma if kind == "f32" else None,
+                        res=res if kind == "f32" else None)
+    bad = np.isnan(got)
+    assert bad[:, 70].all() and bad.sum() == got.shape[0]
+
+
+def test_gemm_mx_nan_operand_block_reaches_exactly_its_mx_row():
+    qa, sa, qw, sw, bias, _, _ = _epilogue_operands()
+    qa, sa = _poison(qa, sa, 100, 1)
+    (q, s), _ = _run_exact("mx", qa, sa, qw, sw, "NaN block in A row 100 -> MX", bias=bias)
+    assert np.all(s[100] == 0xFF) and np.all(q[100] == 0x7F)
+    others = np.arange(q.shape[0]) != 100
+    assert not np.any(s[others] == 0xFF) and not np.any((q[others] & 0x7F) == 0x7F)
+
+
+# ---------------------------------------------------------------------------------------------------- refusals
+def _refused(match, call, *outputs):
+    """`call` must raise M324Error matching `match` and, after a device synchronise, have left every output as it was"""
+    from motion324_amd.lib import M324Error
+    before = [t.clone() for t in outputs]
+    with pytest.raises(M324Error, match=match):
+        call()
+    torch.cuda.synchronize()
+    for t, b in zip(outputs, before):
+        assert torch.equal(t, b), "a refused call wrote to its output"
+
+
+def _filled(shape, dtype):
+    return torch.full(shape, SENT if dtype == torch.uint8 else 7.0, dtype=dtype, device=DEV)
+
+
+def _mx_filled(rows, K):
+    from motion324_amd.ops import MX
+    return MX(_filled((rows, K), torch.uint8), _filled((rows, (K // 32 + 3) // 4 * 4), torch.uint8)[:, :K // 32])
+
+
+def test_gemm_mx_refusals_leave_the_outputs_alone():
+    ops = _ops()
+    from motion324_amd.lib import ACT_GELU
+    from motion324_amd.ops import MX
+    a, w = _mx_filled(128, 128), _mx_filled(128, 128)
+    bf, f32 = _filled((128, 128), torch.bfloat16), _filled((128, 128), torch.float32)
+    vec = _filled((128,), torch.float32)
+    _refused("multiple of 64", lambda: ops.gemm_mx(a, _mx_filled(96, 128), bf), bf)
+    _refused("not built", lambda: ops.gemm_mx(a, w, bf, act=ACT_GELU), bf)
+    _refused("not built", lambda: ops.gemm_mx(a, w, bf, gamma=vec), bf)
+    _refused("not built", lambda: ops.gemm_mx(a, w, f32), f32)
+    other = _filled((128, 128), torch.float32)
+    _refused("not built", lambda: ops.gemm_mx(a, w, f32, residual=other), f32, other)
+    # operand and output views
+    wide = _filled((128, 136), torch.uint8)
+    _refused("operand rows must be 16-byte", lambda: ops.gemm_mx(MX(wide[:, :128], a.s), w, bf), bf)        # lda = 136
+    s6 = _filled((128, 6), torch.uint8)
+    _refused("scale rows 4-byte", lambda: ops.gemm_mx(a, MX(w.q, s6[:, :4]), bf), bf)                       # scale row stride 6
+    bf132 = _filled((128, 132), torch.bfloat16)
+    _refused("bf16 C misaligned", lambda: ops.gemm_mx(a, w, bf132[:, :128]), bf132)                          # ldc = 132
+    narrow = MX(_filled((128, 128), torch.uint8), _filled((128, 3), torch.uint8))
+    _refused(r"MX operand of at least \[128, 128\]", lambda: ops.gemm_mx(a, w, narrow), narrow.q, narrow.s)  # 3 scale bytes for 4 blocks
+
+
+def test_gemm_mx_qkv_heads_refusals_leave_the_outputs_alone():
+    ops = _ops()
+    from motion324_amd.lib import ACT_GELU
+    H = 2
+    w3 = _mx_filled(3 * H * 64, 128)
+    vec = _filled((3 * H * 64,), torch.float32)
+
+    def heads(B, L, vt=False):
+        q, k = _filled((B, H, L, 64), torch.bfloat16), _filled((B, H, L, 64), torch.bfloat16)
+        v = _filled((B, H, 64, L) if vt else (B, H, L, 64), torch.bfloat16)
+        return (q, k, v, None, None, 1e-5, 1.0, L, H), (q, k, v)
+    hv, outs = heads(1, 192, vt=True)                             # L % 64 == 0, so the wrapper lets it through: L % 128 != 0
+    _refused("qkv_L % 128", lambda: ops.gemm_mx(_mx_filled(192, 128), w3, None, qkv_heads=hv), *outs)
+    hn, outs = heads(1, 128)
+    _refused("N=256 vs 3 parts of 2 heads", lambda: ops.gemm_mx(_mx_filled(128, 128), _mx_filled(256, 128), None, qkv_heads=hn), *outs)
+    a = _mx_filled(128, 128)
+    # arguments the q|k|v heads epilogue does not take: refused, never dropped
+    res = _filled((128, 3 * H * 64), torch.float32)
+    _refused("residual= goes with the fp32 residual stream only", lambda: ops.gemm_mx(a, w3, None, qkv_heads=hn, residual=res), res, *outs)
+    _refused("no activation / residual / gamma", lambda: ops.gemm_mx(a, w3, None, qkv_heads=hn, act=ACT_GELU), *outs)
+    _refused("no activation / residual / gamma", lambda: ops.gemm_mx(a, w3, None, qkv_heads=hn, gamma=vec), *outs)
+
+
+def test_gemm_mx_refuses_a_residual_with_an_mx_output():
+    ops = _ops()
+    a, w, out = _mx_filled(128, 128), _mx_filled(128, 128), _mx_filled(128, 128)
+    res = _filled((128, 128), torch.float32)
+    _refused("residual= goes with the fp32 residual stream only", lambda: ops.gemm_mx(a, w, out, residual=res), out.q, out.s, res)
+    _refused("not built", lambda: ops.gemm_mx(a, w, out, gamma=_filled((128,), torch.float32)), out.q, out.s)
+
+
+def test_layernorm_mx_and_mx_quant_refusals_leave_the_outputs_alone():
+    ops = _ops()
+    for C in (48, 1056):
+        out = _mx_filled(4, C)
+        x, w = _filled((4, C), torch.float32), _filled((C,), torch.float32)
+        _refused(f"C={C} ", lambda: ops.layernorm_mx(x, w, None, 1e-6, out), out.q, out.s)
+    out = _mx_filled(4, 64)
+    _refused("x must be fp32", lambda: ops.layernorm_mx(_filled((4, 64), torch.bfloat16), _filled((64,), torch.float32), None, 1e-6, out),
+             out.q, out.s)
+    out = _mx_filled(4, 48)
+    _refused("K=48 ", lambda: ops.mx_quant(_filled((4, 48), torch.float32), out), out.q, out.s)
+    out = _mx_filled(4, 64)
+    _refused("unsupported dtype", lambda: ops.mx_quant(_filled((4, 64), torch.float16), out), out.q, out.s)
+    x34 = _filled((4, 34), torch.float32)
+    out = _mx_filled(4, 32)
+    _refused("x rows must be 16-byte", lambda: ops.mx_quant(x34[:, :32], out), out.q, out.s)                 # row stride 136 bytes
