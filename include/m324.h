@@ -838,6 +838,34 @@ int m324_fvd_prepare(const void* src, int mode, long frames, int H, int W, int H
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A plain ViT image tower in fp32 (csrc/vit.hip; added at ABI 23 without a bump): what open_clip's VisionTransformer needs
+ * besides m324_gemm -- heads of any width, rows wider than 1024, byte images under another normalisation.
+ *   replaces: model.encode_image of open_clip's ViT-bigG-14 at evaluation/calculate_lpips.py:90-136 (the "CLIP Loss" line of
+ *             evaluation/evaluation.py), together with m324_gemm and m324_frame_resample; motion324_amd/clipsim.py is the host.
+ * m324_attention_tok: O = softmax(q k^T * scale) v per (batch, head), fp32, straight from the token-major result of a fused
+ *   in-projection (nn.MultiheadAttention.in_proj order): row b * L + l of qkv (ld elements apart) holds q in columns
+ *   [h * D, (h + 1) * D), k in H * D + the same and v in 2 * H * D + the same.  O[(b * L + l) * ldo + h * D + d]; nothing else of
+ *   O is written.  No split pass, no transposed V and no padding in HBM.  D % 8 == 0, 8 <= D <= 128 (else
+ *   M324_ERR_UNSUPPORTED); ld >= 3 * H * D and ldo >= H * D, both multiples of 4; bases 16-byte aligned; L >= 1; scale > 0.
+ *   The arithmetic is m324_attention's fp32 kernel: scores as k-ordered fp32 fma chains (v_mfma_f32_32x32x2_f32), a running
+ *   maximum over key tiles, exp2f of (score * scale * log2(e) - maximum), fp32 sums, one division per row.
+ * m324_layernorm_wide: m324_layernorm's arithmetic (the mean, then the sum of squared deviations from it) on fp32 in and out
+ *   for C % 4 == 0, 4 <= C <= 4096 (else M324_ERR_UNSUPPORTED); ldx, ldy multiples of 4 and >= C; b may be NULL; y must not
+ *   overlap x.  No row map: a strided selection of rows is a larger ldx (the class-token rows of a [n, L, C] stream: ldx = L * C).
+ * m324_vit_patches: img [F, S, S, 3] uint8 -> out fp32 [F * g * g, Kp], g = S / patch; column c * patch * patch + ky * patch + kx
+ *   (the Conv2d weight's flattening) holds ((float)v / 255.0f - mean[c]) / std[c], each operation one IEEE fp32 operation in
+ *   that order (torchvision's ToTensor, then Normalize); columns 3 * patch * patch .. Kp - 1 are zero.  Kp % 32 == 0 (else
+ *   M324_ERR_UNSUPPORTED).  mean_std: six floats in DEVICE memory, the three means, then the three standard deviations.
+ * m324_vit_tokens: x [F * L, C] from patch_rows [F * (L - 1), C], cls [C] and pos [L, C]: x[f * L] = cls + pos[0],
+ *   x[f * L + 1 + p] = patch_rows[f * (L - 1) + p] + pos[1 + p], one fp32 addition per element.  C % 4 == 0; all dense.
+ * ------------------------------------------------------------------------------------------ */
+int m324_attention_tok(const float* qkv, long ld, float* O, long ldo, int B, int L, int H, int D, float scale, void* stream);
+int m324_layernorm_wide(const float* x, long ldx, const float* w, const float* b, float eps, float* y, long ldy, int rows, int C,
+                        void* stream);
+int m324_vit_patches(const unsigned char* img, int F, int S, int patch, const float* mean_std, float* out, int Kp, void* stream);
+int m324_vit_tokens(const float* patch_rows, const float* cls, const float* pos, float* x, int F, int L, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one
  * topology into a bit grid, the orthographic fill of such a grid, and the popcounts of two grids.  replaces: compute_iou_voxel
  * of the reference's evaluation/evaluation_pcd.py:612-637 (trimesh's subdivision voxeliser on the CPU; the reference keeps the call

@@ -27,6 +27,8 @@ from .lib import M324Error
 
 PRECISION_BITS = 22                       # fixed-point position of the 8-bit resampling coefficients
 LANCZOS_SUPPORT = 3.0
+BICUBIC_SUPPORT = 2.0
+BICUBIC_A = -0.5                          # the cubic's free parameter in the reference library's 8-bit resampling
 
 
 class FramedVideo(NamedTuple):
@@ -45,16 +47,33 @@ def _lanczos(t: float) -> float:
     return (math.sin(a) / a) * (math.sin(b) / b)
 
 
-def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+def _bicubic(t: float) -> float:
+    a = BICUBIC_A
+    t = -t if t < 0.0 else t
+    if t < 1.0:
+        return ((a + 2.0) * t - (a + 3.0)) * t * t + 1
+    if t < 2.0:
+        return (((t - 5) * t + 8) * t - 4) * a
+    return 0.0
+
+
+FILTERS = {"lanczos": (_lanczos, LANCZOS_SUPPORT), "bicubic": (_bicubic, BICUBIC_SUPPORT)}
+
+
+def resample_tables(in_size: int, out_size: int, filter: str = "lanczos") -> Tuple[np.ndarray, np.ndarray]:
     """(coef int32 [out_size, ksize], bounds int32 [out_size, 2] = (first source sample, number of taps)) of one 8-bit Lanczos
     pass from in_size to out_size samples.  The filter is stretched by the scale when shrinking; every output's window is cut
     at the ends of the line, its weights are normalised by their sum (added in tap order) and rounded half away from zero to
-    22 fractional bits.  Unused taps are zero."""
+    22 fractional bits.  Unused taps are zero.  filter "bicubic": the reference library's cubic (a = -0.5, support 2) under the
+    same window, normalisation and rounding rules."""
     if in_size <= 0 or out_size <= 0:
         raise M324Error(f"resample_tables: sizes must be positive, got {in_size} -> {out_size}")
+    if filter not in FILTERS:
+        raise M324Error(f"resample_tables: filter must be one of {sorted(FILTERS)}, got {filter!r}")
+    kernel, kernel_support = FILTERS[filter]
     scale = in_size / out_size
     fs = max(scale, 1.0)
-    support = LANCZOS_SUPPORT * fs
+    support = kernel_support * fs
     ksize = int(math.ceil(support)) * 2 + 1
     coef = np.zeros((out_size, ksize), dtype=np.int32)
     bounds = np.zeros((out_size, 2), dtype=np.int32)
@@ -64,7 +83,7 @@ def resample_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray
         center = (i + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), in_size)
-        weights = [_lanczos((x + xmin - center + 0.5) * inv) for x in range(xmax - xmin)]
+        weights = [kernel((x + xmin - center + 0.5) * inv) for x in range(xmax - xmin)]
         total = 0.0
         for w in weights:
             total += w

@@ -139,6 +139,10 @@ SIGNATURES = {
     "m324_maxpool3d": [_P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "m324_i3d_head": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "m324_fvd_prepare": [_P, _I, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "m324_attention_tok": [_P, _L, _P, _L, _I, _I, _I, _I, _F, _P],
+    "m324_layernorm_wide": [_P, _L, _P, _P, _F, _P, _L, _I, _I, _P],
+    "m324_vit_patches": [_P, _I, _I, _I, _P, _P, _I, _P],
+    "m324_vit_tokens": [_P, _P, _P, _P, _I, _I, _I, _P],
     "m324_transpose": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_colsum": [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "m324_colsum_multi": [C.POINTER(ColsumItem), _I, _P],

@@ -1960,6 +1960,99 @@ def lpips_layer(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, out: Option
     return out
 
 
+# ------------------------------------------------------------------------------------------------ ViT image tower (fp32)
+ATTN_TOK_MAX_D = 128            # m324_attention_tok: D % 8 == 0, 8 <= D <= 128
+LAYERNORM_WIDE_MAX_C = 4096     # m324_layernorm_wide: C % 4 == 0, 4 <= C <= 4096
+
+
+def _f32_rows(t, name: str):
+    _on_device(t, name)
+    if t.dtype != torch.float32:
+        raise L.M324Error(f"{name}: expected fp32, got {t.dtype}")
+    return _rows(t, name)
+
+
+def attention_tok(qkv: torch.Tensor, B: int, L_: int, H: int, D: int, scale: Optional[float] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 self-attention from the token-major q|k|v rows of a fused in-projection (m324_attention_tok): qkv [B * L, >= 3 H D]
+    with q, k, v at columns 0, H D, 2 H D (+ h D); returns out [B * L, >= H D], of which only the first H D columns are
+    written.  scale None: D ** -0.5.  The library refuses the head widths and leading dimensions it does not do."""
+    pq, ld = _f32_rows(qkv, "attention_tok: qkv")
+    B, L_, H, D = int(B), int(L_), int(H), int(D)
+    if out is None:
+        out = torch.empty((B * L_, H * D), dtype=torch.float32, device=qkv.device)
+    po, ldo = _f32_rows(out, "attention_tok: out")
+    if min(B, L_, H, D) < 1 or qkv.shape[0] < B * L_ or out.shape[0] < B * L_ or qkv.shape[1] < 3 * H * D or out.shape[1] < H * D \
+            or out.device != qkv.device:
+        raise L.M324Error(f"attention_tok: qkv{tuple(qkv.shape)} / out{tuple(out.shape)} do not hold B={B} L={L_} H={H} D={D}")
+    scale = D ** -0.5 if scale is None else float(scale)
+    tag = f"attn_tok_kernel | B={B} L={L_} H={H} D={D}" if _timing() else ""
+    with span("attention", 4.0 * B * H * L_ * L_ * D, 4.0 * B * L_ * H * D * 4, tag):
+        _launch("m324_attention_tok", pq, ld, po, ldo, B, L_, H, D, scale)
+    _wrote(out)
+    return out
+
+
+def layernorm_wide(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], eps: float, out: Optional[torch.Tensor] = None,
+                   rows: Optional[int] = None) -> torch.Tensor:
+    """fp32 LayerNorm over the last dimension for C up to 4096 (m324_layernorm_wide): x [>= rows, C] with any leading dimension
+    that is a multiple of 4 (a strided row selection is a view), out [>= rows, C]; rows None: x.shape[0]."""
+    px, ldx = _f32_rows(x, "layernorm_wide: x")
+    Cdim = x.shape[1]
+    rows = x.shape[0] if rows is None else int(rows)
+    if out is None:
+        out = torch.empty((rows, Cdim), dtype=torch.float32, device=x.device)
+    py, ldy = _f32_rows(out, "layernorm_wide: out")
+    if rows < 1 or x.shape[0] < rows or out.shape[0] < rows or out.shape[1] != Cdim or out.device != x.device:
+        raise L.M324Error(f"layernorm_wide: x{tuple(x.shape)} / out{tuple(out.shape)} do not hold {rows} rows of one width")
+    tag = f"layernorm_wide_kernel | rows={rows} C={Cdim}" if _timing() else ""
+    with span("hbm_pass", 0.0, float(rows) * Cdim * 8, tag):
+        _launch("m324_layernorm_wide", px, ldx, _vec(w, Cdim, "layernorm_wide: w"), _vec(b, Cdim, "layernorm_wide: b"), float(eps), py, ldy,
+                rows, Cdim)
+    _wrote(out)
+    return out
+
+
+def vit_patches(img: torch.Tensor, patch: int, mean_std: torch.Tensor, Kp: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Patch rows fp32 [F * g * g, Kp] of square byte images uint8 [F,S,S,3] (m324_vit_patches): ToTensor, then Normalize with
+    mean_std = fp32 [6] on the device (three means, three standard deviations); columns past 3 patch^2 are zero."""
+    _on_device(img, "vit_patches")
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[3] != 3 or img.shape[1] != img.shape[2] or 0 in img.shape:
+        raise L.M324Error(f"vit_patches: expected uint8 [F,S,S,3], got {img.dtype} {tuple(img.shape)}")
+    F_, S = img.shape[0], img.shape[1]
+    patch, Kp = int(patch), int(Kp)
+    if patch < 1 or S % patch:
+        raise L.M324Error(f"vit_patches: the image side {S} is no multiple of the patch {patch}")
+    g = S // patch
+    img = img.detach().contiguous()
+    mean_std = _device_array(mean_std, torch.float32, "vit_patches: mean_std")
+    if mean_std.numel() != 6 or mean_std.device != img.device:
+        raise L.M324Error("vit_patches: mean_std must be fp32 [6] on the images' device")
+    out = _out_like(out, (F_ * g * g, Kp), img.device, "vit_patches")
+    _launch("m324_vit_patches", _p(img), F_, S, patch, _p(mean_std), _p(out), Kp)
+    _wrote(out)
+    return out
+
+
+def vit_tokens(patch_rows: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tower's input stream fp32 [F * L, C] (m324_vit_tokens): per image the class token, then its L - 1 patch rows, each
+    plus its row of pos [L, C]."""
+    for t, name in ((patch_rows, "patch_rows"), (cls, "cls"), (pos, "pos")):
+        _on_device(t, "vit_tokens: " + name)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.M324Error(f"vit_tokens: {name} must be contiguous fp32, got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    if pos.dim() != 2 or patch_rows.dim() != 2 or pos.shape[0] < 2 or patch_rows.shape[1] != pos.shape[1] or cls.numel() != pos.shape[1] \
+            or patch_rows.shape[0] == 0 or patch_rows.shape[0] % (pos.shape[0] - 1):
+        raise L.M324Error(f"vit_tokens: patch_rows{tuple(patch_rows.shape)}, cls{tuple(cls.shape)} and pos{tuple(pos.shape)} do not fit "
+                          f"[F * (L - 1), C], [C] and [L, C]")
+    L_, Cdim = pos.shape
+    F_ = patch_rows.shape[0] // (L_ - 1)
+    out = _out_like(out, (F_ * L_, Cdim), patch_rows.device, "vit_tokens")
+    _launch("m324_vit_tokens", _p(patch_rows), _p(cls), _p(pos), _p(out), F_, L_, Cdim)
+    _wrote(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ foreground matting
 MATTE_SIDES = 6                 # M324_MATTE_SIDES
 MATTE_MAX_SIDE = 16384          # M324_MATTE_MAX_SIDE
