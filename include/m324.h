@@ -27,7 +27,11 @@ extern "C" {
 
 typedef enum { M324_OK = 0, M324_ERR_INVALID = -1, M324_ERR_HIP = -2, M324_ERR_UNSUPPORTED = -3 } m324_status;
 typedef enum { M324_F32 = 0, M324_BF16 = 1, M324_MXFP8 = 2 } m324_dtype;
-typedef enum { M324_ACT_NONE = 0, M324_ACT_GELU = 1 } m324_act;
+typedef enum { M324_ACT_NONE = 0, M324_ACT_GELU = 1, M324_ACT_QUICK_GELU = 2 } m324_act;
+/*   M324_ACT_QUICK_GELU (added at ABI 23 without a bump; OpenAI CLIP's activation): v = acc (+ bias[n]); v = v / (1 + expf(-1.702f * v)),
+ *   one IEEE fp32 product, expf, one addition and one IEEE division: v -> -inf gives -0, never NaN.  Built for fp32 operands
+ *   and an fp32 output on the tile schedules fp32 takes, with a vectorisable output (N % 4 == 0, 16-byte aligned rows); with a
+ *   residual, gamma, a row map, an aux mode, a LayerNorm fold, a batch or any other dtype: M324_ERR_UNSUPPORTED, no launch. */
 /* aux_mode of m324_gemm (aux has the output dtype and layout [M, ldaux], no row remap):
  *   M324_AUX_STORE_PREACT  : aux[m,n] = acc + bias, the value the activation is applied to -- one launch gives the
  *                            MLP both gelu(z) (C) and z (aux), which the backward needs (autograd of transformer.py:73-78);
@@ -62,7 +66,7 @@ int m324_set_tunable(const char* name, int value);
  *             model/Pcd_motion.py:175,284,338-340 (point_embed.mlp, point_normal_rgb_proj, head),
  *             DINOv2 patch_embed.proj / qkv / proj / fc1 / fc2 (model/image_encoder/dino/model_dino.py:160-170,
  *             174-231,338-354).
- *   epilogue, in this order:  v = acc (+ bias[n]) ; v = gelu_erf(v) if act ; v *= gamma[n] ;
+ *   epilogue, in this order:  v = acc (+ bias[n]) ; v = gelu_erf(v) if act is M324_ACT_GELU ; v *= gamma[n] ;
  *                             v += residual[(m % res_rows) * ldr + n]  (fp32 -- except when `residual` IS `C` and out_dtype is
  *                             bf16: then it is the bf16 stream being updated in place) ; store as out_dtype at
  *                             C[out_row(m) * ldc + n],  out_row(m) = (m / row_gin) * row_gout + m % row_gin + row_off.
@@ -864,6 +868,27 @@ int m324_layernorm_wide(const float* x, long ldx, const float* w, const float* b
                         void* stream);
 int m324_vit_patches(const unsigned char* img, int F, int S, int patch, const float* mean_std, float* out, int Kp, void* stream);
 int m324_vit_tokens(const float* patch_rows, const float* cls, const float* pos, float* x, int F, int L, int C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Float resize and fp32 patch rows (csrc/vit.hip; added at ABI 23 without a bump): what DreamSim's three ViT-B/16 towers need in
+ * front of them.  replaces: transforms.Resize((224, 224)) on a float tensor at evaluation/calculate_lpips.py:34-87 -- F.interpolate(
+ * mode="bilinear", align_corners=False, antialias=True) on fp32 values, no 8-bit step -- and the towers' Normalize;
+ * motion324_amd/dreamsim.py is the host and builds the tables (resize_tables, float64 rounded once to fp32).
+ * m324_resample_f32: ONE separable pass.  src is uint8 [F, H, W, 3] (src_u8 != 0; a sample is (float)v / 255.0f, one IEEE fp32
+ *   division: ToTensor) or fp32 planar [F, 3, H, W]; dst is fp32 planar, [F, 3, H, n_out] for axis 0 (x) and [F, 3, n_out, W] for
+ *   axis 1 (y).  weights fp32 [n_out, ksize] and first int32 [n_out] in DEVICE memory: output o is the fp32 fma chain
+ *   acc = fmaf(weights[o][k], sample(first[o] + k), acc), k = 0 .. ksize - 1 in that order from acc = 0; taps at or past the end
+ *   of the axis are skipped (their weights are the zeros behind a row's taps).  Deterministic: no atomics, no order left to the
+ *   hardware; the vectorised forms (16-byte stores; for the y pass 16-byte fp32 loads and 12-byte groups of four byte pixels,
+ *   when W % 4 == 0 and the bases are 16-byte aligned) run the same chains.  first[o] must lie in [0, n_in): the kernel clamps
+ *   it, so a bad table cannot read outside the source.  1 <= ksize <= 64; sides 1 .. 16384; dst must not overlap src.
+ * m324_vit_patches_f32: m324_vit_patches from img fp32 planar [F, 3, S, S]: column c * patch * patch + ky * patch + kx of row
+ *   f * g * g + py * g + px holds (img[f][c][py * patch + ky][px * patch + kx] - mean[c]) / std[c], two IEEE fp32 operations in
+ *   that order (Normalize); columns 3 * patch * patch .. Kp - 1 are zero.  Kp % 32 == 0 (else M324_ERR_UNSUPPORTED).
+ * ------------------------------------------------------------------------------------------ */
+int m324_resample_f32(const void* src, int src_u8, int F, int H, int W, int axis, const float* weights, const int* first, int ksize,
+                      int n_out, float* dst, void* stream);
+int m324_vit_patches_f32(const float* img, int F, int S, int patch, const float* mean_std, float* out, int Kp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Volumetric IoU (csrc/voxel.hip; added at ABI 23 without a bump): exact surface voxelisation of `frames` poses of one

@@ -1167,6 +1167,7 @@ static GemmPlan make_plan(const m324_gemm_args* a) {
     else if (a->aux_mode == M324_AUX_STORE_PREACT || a->aux_mode == M324_AUX_STORE_GELU_GRAD) p.actx = 2;
     else if (a->aux_mode == M324_AUX_MUL_GELU_GRAD || a->aux_mode == M324_AUX_MUL) p.actx = 3;
     else if (a->act == M324_ACT_GELU) p.actx = 1, p.res = res ? 2 : 0;
+    else if (a->act == M324_ACT_QUICK_GELU) p.actx = 6, p.res = 0;      // gemm_validate: fp32, nothing else in the epilogue
     else p.res = res;
     // LayerNorm fold (m324_gemm validated the combination: consumer XOR producer)
     if (a->ln_rowstat) p.actx |= 8, p.res = 0;
@@ -1199,7 +1200,9 @@ template <typename TIN, typename TOUT, int ACTX, int RES>
 static int launch_tile(const m324_gemm_args* a, hipStream_t s, const Epilogue& ep, const GemmPlan& p) {
     constexpr bool bf_in = sizeof(TIN) == 2, bf_out = sizeof(TOUT) == 2;
     constexpr bool n3 = (ACTX & 7) == 5, fold = (ACTX & (8 | 16)) != 0;
-    constexpr bool built = (!(fold || n3) || bf_in) && (!((ACTX & 4) || ACTX == 9 || ACTX == 16) || bf_out) && (ACTX != 48 || !bf_out);
+    constexpr bool heads = (ACTX & 7) == 4, quick = ACTX == 6;          // QuickGELU: fp32 operands and output only
+    constexpr bool built = (!(fold || n3) || bf_in) && (!(heads || n3 || ACTX == 9 || ACTX == 16) || bf_out) && (ACTX != 48 || !bf_out) &&
+                           (!quick || (!bf_in && !bf_out));
 #define M324_TILE(KERNEL, T, TILE_N)                                                                                         \
     hipLaunchKernelGGL(KERNEL, grid, block, 0, s, (const T*)a->A, a->lda, (const T*)a->W, a->ldw, (TOUT*)a->C, a->ldc, a->M, \
                        a->N, a->K, ep, ceil_div(a->N, TILE_N), xcd_mode(a))
@@ -1236,6 +1239,8 @@ int launch(const m324_gemm_args* a, hipStream_t s) {
     const GemmPlan p = make_plan(a);
     const dim3 grid((unsigned)p.wg, (unsigned)p.grid_y), block((unsigned)p.threads);
     int rc = M324_OK;
+    if (a->act == M324_ACT_QUICK_GELU && p.variant != 2 && p.variant != 5)
+        M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: schedule %d has no QuickGELU epilogue (the fp32 tile schedules 2 and 5 do)", p.variant);
     if (p.variant == 15) {
         rc = m324::launch_hp(a, s, ep, p, xcd_mode(a));
     } else if (p.variant == 1) {
@@ -1254,7 +1259,7 @@ int launch(const m324_gemm_args* a, hipStream_t s) {
     case (ACTX) * 4 + (RES): rc = launch_tile<TIN, TOUT, ACTX, RES>(a, s, ep, p); break
         switch (p.actx * 4 + p.res) {
             M324_CODE(0, 0); M324_CODE(0, 1); M324_CODE(0, 2); M324_CODE(1, 0); M324_CODE(1, 2); M324_CODE(2, 0); M324_CODE(3, 0);
-            M324_CODE(4, 0); M324_CODE(5, 0);
+            M324_CODE(4, 0); M324_CODE(5, 0); M324_CODE(6, 0);
             M324_CODE(8, 0); M324_CODE(9, 0); M324_CODE(12, 0); M324_CODE(13, 0);          // behind a folded LayerNorm
             M324_CODE(16, 1); M324_CODE(16, 2); M324_CODE(48, 1); M324_CODE(48, 2);        // producers of its statistics
             default: M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: no kernel for epilogue act=%d res=%d", p.actx, p.res);
@@ -1336,6 +1341,11 @@ static int gemm_validate(const m324_gemm_args* a) {
     M324_REQUIRE(a->batch <= 1 || (vec_ok(a) && !a->residual && a->batch <= 65535),
                  "m324_gemm: a batched launch needs a vectorisable, residual-free problem");
     M324_REQUIRE(a->aux_mode >= 0 && a->aux_mode <= M324_AUX_MUL, "m324_gemm: aux_mode %d", a->aux_mode);
+    if (a->act == M324_ACT_QUICK_GELU &&
+        !(a->in_dtype == M324_F32 && a->out_dtype == M324_F32 && !a->residual && !a->gamma && a->row_gin <= 0 && a->aux_mode == M324_AUX_NONE &&
+          !a->ln_rowstat && !a->ln_stats_out && !a->ln_copy_out && a->batch <= 1 && vec_ok(a)))
+        M324_FAIL(M324_ERR_UNSUPPORTED, "m324_gemm: M324_ACT_QUICK_GELU is built for fp32 operands and a vectorisable fp32 output alone: no "
+                  "residual, gamma, row map, aux mode, LayerNorm fold or batch (in=%d out=%d N=%d)", a->in_dtype, a->out_dtype, a->N);
     if (n3_mode) {
         M324_REQUIRE(a->aux && a->qkv_qw && a->act == M324_ACT_GELU && !a->residual && !a->gamma && a->row_gin <= 0 && a->batch <= 1,
                      "m324_gemm: M324_AUX_N3 = Linear + GELU + [3, N] contraction: aux (partial sums) and qkv_qw (the [3, N] weight) "

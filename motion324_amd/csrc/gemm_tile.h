@@ -223,6 +223,10 @@ __device__ __forceinline__ float gelu_grad(float z) {
     }
 }
 
+// M324_ACT_QUICK_GELU (fp32 only): x sigmoid(1.702 x) as x / (1 + exp(-1.702 x)).  A large negative x makes the exponential
+// +inf and the quotient -0; a large positive one makes it 0 and the quotient x: no NaN at either end.
+__device__ __forceinline__ float quick_gelu(float x) { return __fdiv_rn(x, __fadd_rn(1.0f, expf(__fmul_rn(-1.702f, x)))); }
+
 template <typename TOUT>
 __device__ __forceinline__ float4 load4_out(const TOUT* p) {
     if constexpr (sizeof(TOUT) == 2) {
@@ -665,7 +669,7 @@ __device__ __forceinline__ float2 ln_row_direct(const Epilogue& ep, int M, int r
 }
 
 // ACTX: the low bits are the activation / aux code (0 none, 1 GELU, 2 GELU + pre-activation, 3 x gelu', 4 q|k|v heads,
-// 5 N3 head); bits 3-5 compile the LayerNorm-fold paths in: 8 = consumer (ep.rowstat / ep.colsum), 16 = producer statistics
+// 5 N3 head, 6 QuickGELU -- fp32 in and out, the 4-column `body` only); bits 3-5 compile the LayerNorm-fold paths in: 8 = consumer (ep.rowstat / ep.colsum), 16 = producer statistics
 // (ep.stats), 32 = bf16 twin of an fp32 output (ep.copy).  Template bits, not run-time flags: a run-time `if` inside the
 // unrolled passes splits them into basic blocks, and the loads / stores of a block are then no longer issued as batches
 // (measured: +6 us on a 56 us GEMM whose fold work is 2 FMAs per element); the instantiations without the bits are
@@ -828,6 +832,7 @@ __device__ __forceinline__ void store_tile_lds(const f32x16 (&acc)[MI][2], float
                         store4_out<TOUT>(static_cast<TOUT*>(ep.aux) + (long)m * ep.ldaux + n, keep.x, keep.y, keep.z, keep.w);
                 }
                 if (ACT == 1) apply_gelu4<TOUT>(x);
+                if constexpr (ACT == 6) x = make_float4(quick_gelu(x.x), quick_gelu(x.y), quick_gelu(x.z), quick_gelu(x.w));
                 if (ep.gamma) { x.x *= ga.x; x.y *= ga.y; x.z *= ga.z; x.w *= ga.w; }
                 if (has_res) { x.x += res[p].x; x.y += res[p].y; x.z += res[p].z; x.w += res[p].w; }
                 if constexpr (ACT == 3) {

@@ -199,9 +199,232 @@ __global__ __launch_bounds__(256) void vit_tokens_kernel(const float* __restrict
     *reinterpret_cast<float4*>(x + row * C + c) = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
 }
 
+// ------------------------------------------------------------------------------------------- float resize
+// One separable pass under host-built tables (motion324_amd/dreamsim.py resize_tables).  Every form runs the same chain per
+// output -- acc = fmaf(w[k], sample(first + k), acc) in tap order -- so which form a shape takes never shows in the result.
+// A byte sample is (float)v / 255, one IEEE division (ToTensor).  `first` is clamped into the axis and taps at or past its end
+// are skipped: no table can make a read leave the source.
+__device__ __forceinline__ float byte_sample(unsigned v) { return __fdiv_rn((float)v, 255.0f); }
+
+// source element (f, c, y, x) of either form
+template <bool U8>
+__device__ __forceinline__ float src_at(const void* src, long f, int c, int y, int x, int H, int W) {
+    if constexpr (U8) return byte_sample(static_cast<const unsigned char*>(src)[((f * H + y) * W + x) * 3 + c]);
+    else return static_cast<const float*>(src)[((f * 3 + c) * H + y) * W + x];
+}
+
+// any shape: one thread per output element, consecutive threads along the output row
+template <bool U8, int AXIS>
+__global__ __launch_bounds__(256) void resample_scalar_kernel(const void* __restrict__ src, int H, int W, const float* __restrict__ wt,
+                                                              const int* __restrict__ first, int ksize, int n_out,
+                                                              float* __restrict__ dst, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int OW = AXIS == 0 ? n_out : W, OH = AXIS == 0 ? H : n_out, n_in = AXIS == 0 ? W : H;
+    const int ox = (int)(i % OW);
+    const long r = i / OW;
+    const int oy = (int)(r % OH);
+    const long fc = r / OH;
+    const int c = (int)(fc % 3);
+    const long f = fc / 3;
+    const int o = AXIS == 0 ? ox : oy;
+    const int j0 = min(max(first[o], 0), n_in - 1);
+    const float* w = wt + (long)o * ksize;
+    float acc = 0.f;
+    for (int k = 0; k < ksize && j0 + k < n_in; ++k)
+        acc = fmaf(w[k], AXIS == 0 ? src_at<U8>(src, f, c, oy, j0 + k, H, W) : src_at<U8>(src, f, c, j0 + k, ox, H, W), acc);
+    dst[i] = acc;
+}
+
+// x pass, n_out % 4 == 0: one thread per four consecutive outputs of a row, one 16-byte store.  The taps are gathers (a lane's
+// four windows start scale pixels apart and are not aligned to anything); neighbouring lanes read neighbouring windows of the
+// same source row, so a wave's reads of one tap step fall into a few consecutive cache lines.
+template <bool U8>
+__global__ __launch_bounds__(256) void resample_x4_kernel(const void* __restrict__ src, int H, int W, const float* __restrict__ wt,
+                                                          const int* __restrict__ first, int ksize, int n_out,
+                                                          float* __restrict__ dst, long total4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;           // one float4 of dst
+    if (i >= total4) return;
+    const int O4 = n_out >> 2;
+    const int o0 = (int)(i % O4) * 4;
+    const long r = i / O4;
+    const int y = (int)(r % H);
+    const long fc = r / H;
+    const int c = (int)(fc % 3);
+    const long f = fc / 3;
+    float acc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j0 = min(max(first[o0 + e], 0), W - 1);
+        const float* w = wt + (long)(o0 + e) * ksize;
+        float a = 0.f;
+        for (int k = 0; k < ksize && j0 + k < W; ++k) a = fmaf(w[k], src_at<U8>(src, f, c, y, j0 + k, H, W), a);
+        acc[e] = a;
+    }
+    *reinterpret_cast<float4*>(dst + i * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
+// y pass over fp32 planes, W % 4 == 0: one thread per four consecutive columns; every tap is a 16-byte load from a source row and
+// consecutive lanes read consecutive 16 bytes of it
+__global__ __launch_bounds__(256) void resample_y4_f32_kernel(const float* __restrict__ src, int H, int W, const float* __restrict__ wt,
+                                                              const int* __restrict__ first, int ksize, int n_out,
+                                                              float* __restrict__ dst, long total4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int W4 = W >> 2;
+    const int x = (int)(i % W4) * 4;
+    const long r = i / W4;
+    const int oy = (int)(r % n_out);
+    const long fc = r / n_out;
+    const int j0 = min(max(first[oy], 0), H - 1);
+    const float* w = wt + (long)oy * ksize;
+    const float* s = src + (fc * H + j0) * W + x;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < ksize && j0 + k < H; ++k) {
+        const float4 v = *reinterpret_cast<const float4*>(s + (long)k * W);
+        const float wk = w[k];
+        acc.x = fmaf(wk, v.x, acc.x); acc.y = fmaf(wk, v.y, acc.y); acc.z = fmaf(wk, v.z, acc.z); acc.w = fmaf(wk, v.w, acc.w);
+    }
+    *reinterpret_cast<float4*>(dst + i * 4) = acc;
+}
+
+// y pass over interleaved bytes, W % 4 == 0: one thread per four consecutive pixels = 12 bytes = three aligned words per tap
+// (a wave reads 768 consecutive bytes of a source row), three 16-byte stores, one per plane
+__global__ __launch_bounds__(256) void resample_y4_u8_kernel(const unsigned char* __restrict__ src, int H, int W, const float* __restrict__ wt,
+                                                             const int* __restrict__ first, int ksize, int n_out,
+                                                             float* __restrict__ dst, long total4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;           // (f, oy, x / 4)
+    if (i >= total4) return;
+    const int W4 = W >> 2;
+    const int x = (int)(i % W4) * 4;
+    const long r = i / W4;
+    const int oy = (int)(r % n_out);
+    const long f = r / n_out;
+    const int j0 = min(max(first[oy], 0), H - 1);
+    const float* w = wt + (long)oy * ksize;
+    const unsigned char* s = src + ((f * H + j0) * W + x) * 3;
+    float acc[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) acc[e] = 0.f;
+    for (int k = 0; k < ksize && j0 + k < H; ++k) {
+        const unsigned* p = reinterpret_cast<const unsigned*>(s + (long)k * W * 3);
+        const unsigned u[3] = {p[0], p[1], p[2]};
+        const float wk = w[k];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) acc[e] = fmaf(wk, byte_sample((u[e >> 2] >> (8 * (e & 3))) & 0xFFu), acc[e]);   // byte e = pixel e / 3, channel e % 3
+    }
+    const long plane = (long)n_out * W;
+    float* d = dst + (f * 3 * n_out + oy) * W + x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(d + c * plane) = make_float4(acc[c], acc[3 + c], acc[6 + c], acc[9 + c]);
+}
+
+// ------------------------------------------------------------------------------------------- patch rows from fp32 planes
+// (x - mean) / std as two IEEE operations: no contraction, no reciprocal
+__device__ __forceinline__ float normalise(float x, float mean, float std) { return __fdiv_rn(__fsub_rn(x, mean), std); }
+
+// patch % 4 == 0 (so S % 4 == 0 and 3 patch^2 % 4 == 0): one thread per float4 of the output = four consecutive kx of one patch row,
+// one 16-byte load and one 16-byte store
+__global__ __launch_bounds__(256) void vit_patches_f32x4_kernel(const float* __restrict__ img, int S, int patch, int g,
+                                                                const float* __restrict__ mean_std, float* __restrict__ out, int Kp, long total4) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int K4 = Kp >> 2;
+    const long row = i / K4;
+    const int col = (int)(i - row * K4) * 4;
+    const int pp = patch * patch;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (col < 3 * pp) {
+        const int c = col / pp, k = col - c * pp, ky = k / patch, kx = k - ky * patch;
+        const long f = row / (g * g);
+        const int p = (int)(row - f * g * g), py = p / g, px = p - py * g;
+        const float4 x = *reinterpret_cast<const float4*>(img + ((f * 3 + c) * S + py * patch + ky) * S + px * patch + kx);
+        const float m = mean_std[c], s = mean_std[3 + c];
+        v = make_float4(normalise(x.x, m, s), normalise(x.y, m, s), normalise(x.z, m, s), normalise(x.w, m, s));
+    }
+    *reinterpret_cast<float4*>(out + i * 4) = v;
+}
+
+// any patch size: one thread per output element, as vit_patches_kernel
+__global__ __launch_bounds__(256) void vit_patches_f32_kernel(const float* __restrict__ img, int S, int patch, int g,
+                                                              const float* __restrict__ mean_std, float* __restrict__ out, int Kp, long total) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / Kp;
+    const int col = (int)(i - row * Kp);
+    const int pp = patch * patch;
+    float v = 0.f;
+    if (col < 3 * pp) {
+        const int c = col / pp, k = col - c * pp, ky = k / patch, kx = k - ky * patch;
+        const long f = row / (g * g);
+        const int p = (int)(row - f * g * g), py = p / g, px = p - py * g;
+        v = normalise(img[((f * 3 + c) * S + py * patch + ky) * S + px * patch + kx], mean_std[c], mean_std[3 + c]);
+    }
+    out[i] = v;
+}
+
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
+
+extern "C" int m324_resample_f32(const void* src, int src_u8, int F, int H, int W, int axis, const float* weights, const int* first,
+                                 int ksize, int n_out, float* dst, void* stream) {
+    M324_REQUIRE(src && weights && first && dst, "m324_resample_f32: null pointer");
+    M324_REQUIRE(F > 0 && H >= 1 && H <= 16384 && W >= 1 && W <= 16384 && n_out >= 1 && n_out <= 16384,
+                 "m324_resample_f32: F=%d H=%d W=%d n_out=%d (at least one frame, sides of 1 to 16384)", F, H, W, n_out);
+    M324_REQUIRE(axis == 0 || axis == 1, "m324_resample_f32: axis=%d (0 = x, 1 = y)", axis);
+    M324_REQUIRE(ksize >= 1 && ksize <= 64, "m324_resample_f32: ksize=%d (1 to 64)", ksize);
+    M324_REQUIRE(src_u8 || ((uintptr_t)src & 3) == 0, "m324_resample_f32: an fp32 source must be 4-byte aligned");
+    M324_REQUIRE(((uintptr_t)dst & 3) == 0 && ((uintptr_t)weights & 3) == 0 && ((uintptr_t)first & 3) == 0, "m324_resample_f32: misaligned operand");
+    const long OH = axis == 0 ? H : n_out, OW = axis == 0 ? n_out : W;
+    const long total = (long)F * 3 * OH * OW;
+    M324_REQUIRE(total < (1l << 39) && (long)F * 3 * H * W < (1l << 39), "m324_resample_f32: image too large");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 block(256);
+#define RS_GRID(n) dim3((unsigned)(((n) + 255) / 256))
+    if (axis == 0 && n_out % 4 == 0 && aligned16(dst)) {
+        const long t4 = total / 4;
+        if (src_u8) hipLaunchKernelGGL(resample_x4_kernel<true>, RS_GRID(t4), block, 0, s, src, H, W, weights, first, ksize, n_out, dst, t4);
+        else hipLaunchKernelGGL(resample_x4_kernel<false>, RS_GRID(t4), block, 0, s, src, H, W, weights, first, ksize, n_out, dst, t4);
+    } else if (axis == 1 && W % 4 == 0 && aligned16(dst) && aligned16(src)) {
+        if (src_u8) {
+            const long t4 = (long)F * n_out * (W / 4);
+            hipLaunchKernelGGL(resample_y4_u8_kernel, RS_GRID(t4), block, 0, s, (const unsigned char*)src, H, W, weights, first, ksize, n_out, dst, t4);
+        } else {
+            const long t4 = total / 4;
+            hipLaunchKernelGGL(resample_y4_f32_kernel, RS_GRID(t4), block, 0, s, (const float*)src, H, W, weights, first, ksize, n_out, dst, t4);
+        }
+    } else {
+#define RS_SCALAR(u8, ax) hipLaunchKernelGGL((resample_scalar_kernel<u8, ax>), RS_GRID(total), block, 0, s, src, H, W, weights, first, ksize, n_out, dst, total)
+        if (src_u8 && axis == 0) RS_SCALAR(true, 0);
+        else if (src_u8) RS_SCALAR(true, 1);
+        else if (axis == 0) RS_SCALAR(false, 0);
+        else RS_SCALAR(false, 1);
+#undef RS_SCALAR
+    }
+#undef RS_GRID
+    M324_CHECK_LAUNCH("m324_resample_f32");
+    return M324_OK;
+}
+
+extern "C" int m324_vit_patches_f32(const float* img, int F, int S, int patch, const float* mean_std, float* out, int Kp, void* stream) {
+    M324_REQUIRE(img && mean_std && out, "m324_vit_patches_f32: null pointer");
+    M324_REQUIRE(F > 0 && patch > 0 && S >= patch && S <= 16384 && S % patch == 0, "m324_vit_patches_f32: F=%d S=%d patch=%d (S a multiple of patch, at most 16384)",
+                 F, S, patch);
+    if (Kp % 32 != 0 || Kp < 3 * patch * patch) M324_FAIL(M324_ERR_UNSUPPORTED, "m324_vit_patches_f32: Kp=%d (Kp %% 32 == 0, at least 3 patch^2 = %d)", Kp, 3 * patch * patch);
+    M324_REQUIRE(((uintptr_t)img & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)mean_std & 3) == 0, "m324_vit_patches_f32: misaligned operand");
+    const int g = S / patch;
+    const long total = (long)F * g * g * Kp;
+    M324_REQUIRE(total < (1l << 39), "m324_vit_patches_f32: output too large");
+    if (patch % 4 == 0 && aligned16(img) && aligned16(out))
+        hipLaunchKernelGGL(vit_patches_f32x4_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, S, patch, g,
+                           mean_std, out, Kp, total / 4);
+    else
+        hipLaunchKernelGGL(vit_patches_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, S, patch, g,
+                           mean_std, out, Kp, total);
+    M324_CHECK_LAUNCH("m324_vit_patches_f32");
+    return M324_OK;
+}
 
 extern "C" int m324_attention_tok(const float* qkv, long ld, float* O, long ldo, int B, int L, int H, int D, float scale, void* stream) {
     M324_REQUIRE(qkv && O, "m324_attention_tok: null pointer");

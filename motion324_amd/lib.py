@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("M324_LIB") or os.path.join(HERE, "libm324.so")      # M324_LIB: lab builds (tools/lablibs)
 
 F32, BF16, MXFP8 = 0, 1, 2
-ACT_NONE, ACT_GELU = 0, 1
+ACT_NONE, ACT_GELU, ACT_QUICK_GELU = 0, 1, 2
 ABI_VERSION = 23
 ERR_UNSUPPORTED = -3          # m324_status M324_ERR_UNSUPPORTED
 
@@ -143,6 +143,8 @@ SIGNATURES = {
     "m324_layernorm_wide": [_P, _L, _P, _P, _F, _P, _L, _I, _I, _P],
     "m324_vit_patches": [_P, _I, _I, _I, _P, _P, _I, _P],
     "m324_vit_tokens": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "m324_resample_f32": [_P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P],
+    "m324_vit_patches_f32": [_P, _I, _I, _I, _P, _P, _I, _P],
     "m324_transpose": [_P, _L, _P, _L, _I, _I, _I, _I, _P],
     "m324_colsum": [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P],
     "m324_colsum_multi": [C.POINTER(ColsumItem), _I, _P],

@@ -2053,8 +2053,66 @@ def vit_tokens(patch_rows: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, o
     return out
 
 
+RESAMPLE_MAX_SIDE = 16384       # m324_resample_f32: sides of 1 to 16384
+RESAMPLE_MAX_KSIZE = 64         # m324_resample_f32: 1 <= ksize <= 64
+RESAMPLE_AXES = {"x": 0, "y": 1}
+
+
+def resample_f32(src: torch.Tensor, weights: torch.Tensor, first: torch.Tensor, axis: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One separable pass of a float resize (m324_resample_f32): src uint8 [F,H,W,3] (a sample is v / 255 in fp32) or fp32 planar
+    [F,3,H,W]; weights fp32 [n_out, ksize] and first int32 [n_out] on the device (dreamsim.resize_tables); returns fp32 planar
+    [F,3,H,n_out] (axis "x") or [F,3,n_out,W] (axis "y"): per output an fp32 fma chain in tap order."""
+    _on_device(src, "resample_f32")
+    if axis not in RESAMPLE_AXES:
+        raise L.M324Error(f"resample_f32: axis must be 'x' or 'y', got {axis!r}")
+    if src.dim() == 4 and src.dtype == torch.uint8 and src.shape[3] == 3:
+        F_, H, W, u8 = src.shape[0], src.shape[1], src.shape[2], 1
+    elif src.dim() == 4 and src.dtype == torch.float32 and src.shape[1] == 3:
+        F_, H, W, u8 = src.shape[0], src.shape[2], src.shape[3], 0
+    else:
+        raise L.M324Error(f"resample_f32: expected uint8 [F,H,W,3] or fp32 [F,3,H,W], got {getattr(src, 'dtype', None)} {tuple(src.shape)}")
+    if F_ < 1 or not 1 <= H <= RESAMPLE_MAX_SIDE or not 1 <= W <= RESAMPLE_MAX_SIDE:
+        raise L.M324Error(f"resample_f32: at least one frame and sides of 1 to {RESAMPLE_MAX_SIDE}, got {tuple(src.shape)}")
+    src = src.detach().contiguous()
+    weights = _device_array(weights, torch.float32, "resample_f32: weights")
+    first = _device_array(first, torch.int32, "resample_f32: first")
+    if weights.dim() != 2 or first.dim() != 1 or first.shape[0] != weights.shape[0] or weights.device != src.device or first.device != src.device \
+            or not 1 <= weights.shape[0] <= RESAMPLE_MAX_SIDE or not 1 <= weights.shape[1] <= RESAMPLE_MAX_KSIZE:
+        raise L.M324Error(f"resample_f32: weights{tuple(weights.shape)} / first{tuple(first.shape)} must be fp32 [n_out, ksize] and int32 [n_out] "
+                          f"on the source's device (n_out up to {RESAMPLE_MAX_SIDE}, ksize up to {RESAMPLE_MAX_KSIZE})")
+    n_out, ksize = weights.shape
+    ax = RESAMPLE_AXES[axis]
+    out = _out_like(out, (F_, 3, H, n_out) if ax == 0 else (F_, 3, n_out, W), src.device, "resample_f32")
+    if out.data_ptr() == src.data_ptr():
+        raise L.M324Error("resample_f32: out must not be the source")
+    _launch("m324_resample_f32", _p(src), u8, F_, H, W, ax, _p(weights), _p(first), ksize, n_out, _p(out))
+    _wrote(out)
+    return out
+
+
+def vit_patches_f32(img: torch.Tensor, patch: int, mean_std: torch.Tensor, Kp: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Patch rows fp32 [F * g * g, Kp] of square fp32 planar images [F,3,S,S] (m324_vit_patches_f32): (x - mean) / std with
+    mean_std = fp32 [6] on the device, vit_patches' column order; columns past 3 patch^2 are zero."""
+    _on_device(img, "vit_patches_f32")
+    if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3] or 0 in img.shape:
+        raise L.M324Error(f"vit_patches_f32: expected fp32 [F,3,S,S], got {img.dtype} {tuple(img.shape)}")
+    F_, S = img.shape[0], img.shape[2]
+    patch, Kp = int(patch), int(Kp)
+    if patch < 1 or S % patch:
+        raise L.M324Error(f"vit_patches_f32: the image side {S} is no multiple of the patch {patch}")
+    g = S // patch
+    img = img.detach().contiguous()
+    mean_std = _device_array(mean_std, torch.float32, "vit_patches_f32: mean_std")
+    if mean_std.numel() != 6 or mean_std.device != img.device:
+        raise L.M324Error("vit_patches_f32: mean_std must be fp32 [6] on the images' device")
+    out = _out_like(out, (F_ * g * g, Kp), img.device, "vit_patches_f32")
+    _launch("m324_vit_patches_f32", _p(img), F_, S, patch, _p(mean_std), _p(out), Kp)
+    _wrote(out)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ foreground matting
-MATTE_SIDES = 6                 # M324_MATTE_SIDES
+MATTE_SIDES = 6                # M324_MATTE_SIDES
 MATTE_MAX_SIDE = 16384          # M324_MATTE_MAX_SIDE
 MATTE_CHUNKS = 64               # M324_MATTE_CHUNKS: runs per frame of the two-level per-frame reductions
 
