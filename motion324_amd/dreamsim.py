@@ -19,30 +19,20 @@ be settled: whether the DINO feature is the class row after the final norm (feat
 from __future__ import annotations
 
 import argparse
-import math
 import os
 import re
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import ops
-from .clipsim import (GEMM_K, MAX_HEAD, MAX_WIDTH, OPENAI_MEAN, OPENAI_STD, ClipBlock, ClipVisionWeights, _load_file, _pad_k, _round_up,
-                      frames_form, load_clip_vision_weights)
-from .lib import ACT_GELU, ACT_QUICK_GELU, M324Error
+from .lib import M324Error
 from .perceptual import ClipScore, clip_statistics, load_frames, subvideo_frames
+from .vit import (CLIP_LN_EPS, DEFAULT_MAX_SCRATCH_BYTES, DINO_HEADS_BY_WIDTH, DINO_LN_EPS, FEATURES, IMAGENET_MEAN, IMAGENET_STD, OPENAI_MEAN,
+                  OPENAI_STD, TAPS, VitTower, VitWeights, frames_form, load_vit_weights, state_of, synth_dino_state_dict, tensor_of)
 
-IMAGENET_MEAN = (0.485, 0.456, 0.406)
-IMAGENET_STD = (0.229, 0.224, 0.225)
-DINO_LN_EPS = 1e-6                      # timm's VisionTransformer: partial(nn.LayerNorm, eps=1e-6)
-CLIP_LN_EPS = 1e-5
-DEFAULT_MAX_SCRATCH_BYTES = 2 << 30
 RESIZE_SCRATCH_BYTES = 256 << 20        # the intermediate of the first resize pass, per chunk of frames
-TAPS = ("embed", "block0", "last_block", "cls_row")
-FEATURES = ("embedding", "cls", "cls_prenorm")
-ACTS = {"gelu": ACT_GELU, "quick_gelu": ACT_QUICK_GELU}
-DINO_HEADS_BY_WIDTH = {192: 3, 384: 6, 768: 12, 1024: 16}             # timm's ViT-Ti / S / B / L
 
 
 # ------------------------------------------------------------------------------------------- resize tables
@@ -138,147 +128,7 @@ def resize(frames: torch.Tensor, size, antialias: bool = True) -> torch.Tensor:
     return out
 
 
-# ------------------------------------------------------------------------------------------- weights
-class VitWeights(NamedTuple):
-    """fp32 CPU tensors in the layouts the kernels take; every GEMM weight is [N, K padded to a multiple of 32 with zeros]"""
-    width: int
-    heads: int
-    layers: int
-    mlp: int
-    patch: int
-    image: int
-    tokens: int
-    embed: int             # 0: no projection
-    patch_w: torch.Tensor  # [W, Kp]
-    patch_b: Optional[torch.Tensor]     # [W] or None
-    cls: torch.Tensor      # [W]
-    pos: torch.Tensor      # [L, W]
-    ln_pre: Optional[tuple]
-    blocks: tuple          # of ClipBlock: (ln_1, in_proj, out_proj, ln_2, c_fc, c_proj)
-    ln_post: tuple         # the final norm
-    proj_t: Optional[torch.Tensor]      # [E, Wp] or None
-
-
-def _from_clip(w: ClipVisionWeights) -> VitWeights:
-    return VitWeights(w.width, w.heads, w.layers, w.mlp, w.patch, w.image, w.tokens, w.embed, w.patch_w, None, w.cls, w.pos, w.ln_pre,
-                      w.blocks, w.ln_post, w.proj_t)
-
-
-def _tensor(v) -> torch.Tensor:
-    return v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-
-
-_DINO_ANCHOR = "patch_embed.proj.weight"
-
-
-def _layout_of(state: dict) -> str:
-    if any(k.endswith(_DINO_ANCHOR) for k in state):
-        return "dino"
-    if any(k.endswith("conv1.weight") for k in state):
-        return "open_clip"
-    raise M324Error("load_vit_weights: the state dict has neither 'conv1.weight' (open_clip layout) nor 'patch_embed.proj.weight' "
-                    "(DINO / timm layout)")
-
-
-def load_vit_weights(state_or_path, layout: Optional[str] = None, heads: Optional[int] = None) -> VitWeights:
-    """A ViT tower's weights, checked and repacked once.  Two layouts, told apart by their keys (or `layout`): "open_clip"
-    (conv1.weight, transformer.resblocks.*, ln_pre, ln_post, proj: load_clip_vision_weights does it) and "dino" (timm's
-    VisionTransformer: cls_token [1,1,W], pos_embed [1,L,W], patch_embed.proj.{weight,bias}, blocks.{i}.norm1 / attn.qkv /
-    attn.proj / norm2 / mlp.fc1 / mlp.fc2, norm, and optionally norm_pre.* and proj [W, E]).  attn.qkv's rows are q | k | v, each
-    head-major: nn.MultiheadAttention's in-projection order.  Whatever prefix stands in front of patch_embed.proj.weight is
-    stripped from every key.  The head count is not in a state dict: `heads`, or the named towers by width.  What the tower
-    does not do is refused by the key or shape that shows it."""
-    who = "load_vit_weights"
-    state = _load_file(os.fspath(state_or_path)) if isinstance(state_or_path, (str, os.PathLike)) else state_or_path
-    if not isinstance(state, dict):
-        raise M324Error(f"{who}: expected a state dict or a path to one")
-    layout = _layout_of(state) if layout is None else layout
-    if layout == "open_clip":
-        return _from_clip(load_clip_vision_weights(state, heads=heads))
-    if layout != "dino":
-        raise M324Error(f"{who}: layout must be 'open_clip' or 'dino', got {layout!r}")
-    anchors = [k for k in state if k.endswith(_DINO_ANCHOR)]
-    if len(anchors) != 1:
-        raise M324Error(f"{who}: expected one key ending in {_DINO_ANCHOR!r}, found {sorted(anchors)}")
-    prefix = anchors[0][:-len(_DINO_ANCHOR)]
-    vis = {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)}
-    for k in vis:
-        if re.search(r"(^|\.)(ls1|ls2|gamma_1|gamma_2)(\.|$)", k):
-            raise M324Error(f"{who}: key {k!r}: layer scale is not part of this tower")
-        if k.startswith(("reg_token", "register_tokens", "dist_token")):
-            raise M324Error(f"{who}: key {k!r}: register / distillation tokens are not part of this tower")
-
-    def get(key, shape=None, dims=None):
-        if key not in vis:
-            raise M324Error(f"{who}: the state dict has no key {key!r}")
-        t = _tensor(vis[key])
-        if (shape is not None and tuple(t.shape) != tuple(shape)) or (dims is not None and t.dim() != dims):
-            want = tuple(shape) if shape is not None else f"{dims} dimensions"
-            raise M324Error(f"{who}: {key!r} has shape {tuple(t.shape)}, expected {want}")
-        t = t.detach().to(torch.float32).cpu()
-        if not torch.isfinite(t).all():
-            raise M324Error(f"{who}: {key!r} holds values that are not finite")
-        return t.contiguous()
-
-    conv = get(_DINO_ANCHOR, dims=4)
-    W, cin, p, p2 = conv.shape
-    if cin != 3 or p != p2:
-        raise M324Error(f"{who}: {_DINO_ANCHOR!r} has shape {tuple(conv.shape)}, expected [W, 3, patch, patch]")
-    if W > MAX_WIDTH:
-        raise M324Error(f"{who}: {_DINO_ANCHOR!r} {tuple(conv.shape)}: width {W}: W > {MAX_WIDTH} is not supported")
-    if W % 4:
-        raise M324Error(f"{who}: {_DINO_ANCHOR!r} {tuple(conv.shape)}: width {W} is no multiple of 4")
-    pos = get("pos_embed", dims=3)
-    L = pos.shape[1]
-    g = math.isqrt(max(L - 1, 0))
-    if pos.shape[0] != 1 or pos.shape[2] != W or L < 2 or g * g != L - 1:
-        raise M324Error(f"{who}: 'pos_embed' has shape {tuple(pos.shape)}: expected [1, 1 + g * g, {W}], a class token and a square grid "
-                        f"(a non-square grid is not supported)")
-    if heads is None:
-        if W not in DINO_HEADS_BY_WIDTH:
-            raise M324Error(f"{who}: the head count is not part of a state dict and width {W} is none of the named towers "
-                            f"{sorted(DINO_HEADS_BY_WIDTH)}; pass heads=")
-        heads = DINO_HEADS_BY_WIDTH[W]
-    heads = int(heads)
-    if heads < 1 or W % heads:
-        raise M324Error(f"{who}: width {W} is not divisible by heads={heads} (W % heads != 0)")
-    D = W // heads
-    if D % 8:
-        raise M324Error(f"{who}: 'blocks.0.attn.qkv.weight': head width {D} = {W} / {heads}: D % 8 != 0 is not supported")
-    if D > MAX_HEAD:
-        raise M324Error(f"{who}: 'blocks.0.attn.qkv.weight': head width {D} = {W} / {heads}: D > {MAX_HEAD} is not supported")
-    layers = 0
-    while f"blocks.{layers}.norm1.weight" in vis:
-        layers += 1
-    if layers == 0:
-        raise M324Error(f"{who}: the state dict has no key 'blocks.0.norm1.weight'")
-    mlp = get("blocks.0.mlp.fc1.weight", dims=2).shape[0]
-    if mlp % 4:
-        raise M324Error(f"{who}: 'blocks.0.mlp.fc1.weight': an MLP width of {mlp} is no multiple of 4")
-
-    def ln(name):
-        return get(name + ".weight", (W,)), get(name + ".bias", (W,))
-
-    def linear(name, n, k):
-        return _pad_k(get(name + ".weight", (n, k))), get(name + ".bias", (n,))
-
-    blocks = []
-    for i in range(layers):
-        b = f"blocks.{i}."
-        blocks.append(ClipBlock(ln(b + "norm1"), linear(b + "attn.qkv", 3 * W, W), linear(b + "attn.proj", W, W), ln(b + "norm2"),
-                                linear(b + "mlp.fc1", mlp, W), linear(b + "mlp.fc2", W, mlp)))
-    ln_pre = ln("norm_pre") if "norm_pre.weight" in vis else None
-    proj_t, embed = None, 0
-    if "proj" in vis:
-        proj = get("proj", dims=2)
-        if proj.shape[0] != W or proj.shape[1] % 4:
-            raise M324Error(f"{who}: 'proj' has shape {tuple(proj.shape)}, expected [{W}, E] with E a multiple of 4")
-        proj_t, embed = _pad_k(proj.t()), proj.shape[1]
-    return VitWeights(W, heads, layers, mlp, p, g * p, L, embed, _pad_k(conv.reshape(W, 3 * p * p)), get("patch_embed.proj.bias", (W,)),
-                      get("cls_token", (1, 1, W)).reshape(W).contiguous(), pos.reshape(L, W).contiguous(), ln_pre, tuple(blocks),
-                      ln("norm"), proj_t)
-
-
+# ------------------------------------------------------------------------------------------- LoRA
 _LORA_KEY = re.compile(r"^(?P<module>.+)\.lora_(?P<which>[AB])(?:\.[^.]+)?\.weight$")
 
 
@@ -295,7 +145,7 @@ def merge_lora(state: dict, adapter_state: dict, alpha: float) -> dict:
             if "lora_" in k:
                 raise M324Error(f"{who}: adapter key {k!r} is not <module>.lora_A / lora_B[.<name>].weight")
             continue
-        pairs.setdefault(m["module"], {})[m["which"]] = (k, _tensor(v).detach().to(torch.float64).cpu())
+        pairs.setdefault(m["module"], {})[m["which"]] = (k, tensor_of(v).detach().to(torch.float64).cpu())
     out = dict(state)
     for module, ab in sorted(pairs.items()):
         if set(ab) != {"A", "B"}:
@@ -307,7 +157,7 @@ def merge_lora(state: dict, adapter_state: dict, alpha: float) -> dict:
         if len(hits) != 1:
             raise M324Error(f"{who}: adapter key {ka!r} matches {'no' if not hits else 'more than one'} base weight "
                             f"(looked for a key ending in {tail + '.weight'!r})")
-        base = _tensor(state[hits[0]])
+        base = tensor_of(state[hits[0]])
         if A.dim() != 2 or B.dim() != 2 or A.shape[0] != B.shape[1] or A.shape[0] < 1 or tuple(base.shape) != (B.shape[0], A.shape[1]):
             raise M324Error(f"{who}: adapter key {ka!r}: lora_A {tuple(A.shape)} and lora_B {tuple(B.shape)} do not fit the base weight "
                             f"{hits[0]!r} {tuple(base.shape)}")
@@ -317,182 +167,6 @@ def merge_lora(state: dict, adapter_state: dict, alpha: float) -> dict:
             raise M324Error(f"{who}: adapter key {ka!r}: the merged weight is not finite")
         out[hits[0]] = merged.to(base.dtype if base.dtype.is_floating_point else torch.float32)
     return out
-
-
-def synth_dino_state_dict(seed: int, width: int, layers: int, heads: int, mlp: int, patch: int, image: int, embed: int = 0,
-                          norm_pre: bool = False) -> dict:
-    """Seeded weights in the form of a timm VisionTransformer state dict (no prefix), of trained-like scale, for tests and timing,
-    in the manner of clipsim.synth_clip_state_dict: Linear weights randn / sqrt(fan-in) (the q and k rows of attn.qkv twice that,
-    so that the softmax is not flat), LayerNorm weights around 1, small biases.  The patch projection, its bias, the class token
-    and the positions have size 0.1 and nothing normalises them before block 0: norm1 of block 0 sees a variance near 0.03, where
-    an eps of 1e-5 in place of 1e-6 moves the result by 1e-4 relative -- far outside an fp32 band."""
-    if width % heads or image % patch:
-        raise M324Error(f"synth_dino_state_dict: width {width} / heads {heads} or image {image} / patch {patch} does not divide")
-    g = torch.Generator().manual_seed(int(seed))
-
-    def randn(*shape, scale=1.0):
-        return torch.randn(shape, generator=g) * scale
-
-    L = (image // patch) ** 2 + 1
-    sd = {"cls_token": randn(1, 1, width, scale=0.1), "pos_embed": randn(1, L, width, scale=0.1),
-          "patch_embed.proj.weight": randn(width, 3, patch, patch, scale=0.1 / math.sqrt(3 * patch * patch)),
-          "patch_embed.proj.bias": randn(width, scale=0.1)}
-    if norm_pre:
-        sd["norm_pre.weight"] = 1.0 + randn(width, scale=0.1)
-        sd["norm_pre.bias"] = randn(width, scale=0.05)
-    for i in range(layers):
-        b = f"blocks.{i}."
-        for n in ("norm1", "norm2"):
-            sd[b + n + ".weight"] = 1.0 + randn(width, scale=0.1)
-            sd[b + n + ".bias"] = randn(width, scale=0.05)
-        w = randn(3 * width, width, scale=1.0 / math.sqrt(width))
-        w[:2 * width] *= 2.0
-        sd[b + "attn.qkv.weight"] = w
-        sd[b + "attn.qkv.bias"] = randn(3 * width, scale=0.05)
-        sd[b + "attn.proj.weight"] = randn(width, width, scale=1.0 / math.sqrt(width))
-        sd[b + "attn.proj.bias"] = randn(width, scale=0.05)
-        sd[b + "mlp.fc1.weight"] = randn(mlp, width, scale=1.0 / math.sqrt(width))
-        sd[b + "mlp.fc1.bias"] = randn(mlp, scale=0.05)
-        sd[b + "mlp.fc2.weight"] = randn(width, mlp, scale=1.0 / math.sqrt(mlp))
-        sd[b + "mlp.fc2.bias"] = randn(width, scale=0.05)
-    sd["norm.weight"] = 1.0 + randn(width, scale=0.1)
-    sd["norm.bias"] = randn(width, scale=0.05)
-    if embed:
-        sd["proj"] = randn(width, embed, scale=1.0 / math.sqrt(width))
-    return sd
-
-
-# ------------------------------------------------------------------------------------------- the tower
-class VitTower:
-    """tower = VitTower(weights, device, act=, ln_eps=, mean=, std=, feature=); tower.features(img) -> fp32 [F, E] of fp32 planar
-    images [F,3,S,S] that are already S = tower.image pixels a side and in [0, 1]: the tower normalises them itself, in its patch
-    rows.  feature: "embedding" = the class row after the last LayerNorm times proj (open_clip's encode_image), "cls" = the
-    class row after the final norm, "cls_prenorm" = the class row of the last block's output.  weights: a VitWeights, or whatever
-    load_vit_weights accepts."""
-
-    def __init__(self, weights, device="cuda", act: str = "gelu", ln_eps: float = CLIP_LN_EPS, mean=OPENAI_MEAN, std=OPENAI_STD,
-                 feature: str = "embedding"):
-        if act not in ACTS:
-            raise M324Error(f"VitTower: act must be 'gelu' or 'quick_gelu', got {act!r}")
-        if feature not in FEATURES:
-            raise M324Error(f"VitTower: feature must be one of {FEATURES}, got {feature!r}")
-        if not isinstance(weights, VitWeights):
-            weights = load_vit_weights(weights)
-        if feature == "embedding" and weights.proj_t is None:
-            raise M324Error("VitTower: feature='embedding' needs a 'proj' in the weights")
-        if len(mean) != 3 or len(std) != 3 or any(float(s) == 0.0 for s in std) or not float(ln_eps) > 0.0:
-            raise M324Error("VitTower: mean and std are three numbers each (std not zero) and ln_eps is positive")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise M324Error("VitTower: needs a HIP device (there is no CPU path)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        w = weights
-        self.width, self.heads, self.layers, self.mlp, self.patch, self.image, self.tokens, self.embed = w[:8]
-        self.head_dim = self.width // self.heads
-        self.act, self.act_code, self.ln_eps, self.feature = act, ACTS[act], float(ln_eps), feature
-        self.out_dim = self.embed if feature == "embedding" else self.width
-        dev = self.device
-
-        def to(t):
-            return None if t is None else tuple(x.to(dev) for x in t) if isinstance(t, tuple) else t.to(dev)
-
-        self.patch_w, self.patch_b, self.cls, self.pos, self.proj_t = to(w.patch_w), to(w.patch_b), to(w.cls), to(w.pos), to(w.proj_t)
-        self.ln_pre, self.ln_post = to(w.ln_pre), to(w.ln_post)
-        self.blocks = tuple(ClipBlock(*(to(part) for part in blk)) for blk in w.blocks)
-        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
-        self.mean_std = torch.tensor(self.mean + self.std, dtype=torch.float32, device=dev)
-        self.Kp, self.Wp, self.Mp = self.patch_w.shape[1], _round_up(self.width, GEMM_K), _round_up(self.mlp, GEMM_K)
-
-    def bytes_per_image(self) -> int:
-        """scratch of one image in a chunk: the patch rows and their projection, the stream, the normalised / attended rows,
-        q|k|v and the MLP's hidden rows"""
-        L, W = self.tokens, self.width
-        return 4 * ((L - 1) * (self.Kp + W) + L * (W + self.Wp + 3 * W + self.Mp))
-
-    def images_per_chunk(self, n_images: int, max_scratch_bytes: int) -> int:
-        per = self.bytes_per_image()
-        if per > int(max_scratch_bytes):
-            raise M324Error(f"VitTower: one image needs {per} scratch bytes, max_scratch_bytes is {max_scratch_bytes}")
-        return max(1, min(int(n_images), int(max_scratch_bytes) // per))
-
-    def features(self, img, taps: bool = False, max_scratch_bytes: int = DEFAULT_MAX_SCRATCH_BYTES, stage_events=None):
-        """img: fp32 planar [F,3,S,S], S = self.image, on the tower's device.  Returns fp32 [F, out_dim]; with taps also a dict of
-        the stream [F, L, W] after the embedding or norm_pre ("embed"), after block 0 ("block0") and after the last block
-        ("last_block"), and the class rows [F, W] the feature is made of ("cls_row").  The images pass the tower
-        `images_per_chunk` at a time; the result does not depend on the chunking and nothing synchronises.  stage_events: a list
-        that receives (label, start, end) device events."""
-        if not isinstance(img, torch.Tensor) or not img.is_cuda or img.device != self.device:
-            raise M324Error(f"VitTower: the images must be on {self.device} (there is no CPU path)")
-        if img.dtype != torch.float32 or img.dim() != 4 or tuple(img.shape[1:]) != (3, self.image, self.image) or img.shape[0] < 1:
-            raise M324Error(f"VitTower: expected fp32 [F,3,{self.image},{self.image}], got {img.dtype} {tuple(img.shape)}")
-        T = img.shape[0]
-        img = img.detach().contiguous()
-        n = self.images_per_chunk(T, max_scratch_bytes)
-        L, W, dev = self.tokens, self.width, self.device
-        f32 = torch.float32
-        # y and hid keep zeros in their K-padding columns: the kernels write the first W (mlp) columns only
-        bufs = {"rows": torch.empty((n * (L - 1), self.Kp), dtype=f32, device=dev), "pe": torch.empty((n * (L - 1), W), dtype=f32, device=dev),
-                "x": torch.empty((n * L, W), dtype=f32, device=dev), "y": torch.zeros((n * L, self.Wp), dtype=f32, device=dev),
-                "qkv": torch.empty((n * L, 3 * W), dtype=f32, device=dev), "hid": torch.zeros((n * L, self.Mp), dtype=f32, device=dev),
-                "pooled": torch.zeros((n, self.Wp), dtype=f32, device=dev)}
-        out = torch.empty((T, self.out_dim), dtype=f32, device=dev)
-        tap = {k: torch.empty((T, L, W) if k != "cls_row" else (T, W), dtype=f32, device=dev) for k in TAPS} if taps else None
-        for t0 in range(0, T, n):
-            t1 = min(T, t0 + n)
-            self._chunk(img[t0:t1], bufs, out[t0:t1], {k: v[t0:t1] for k, v in tap.items()} if taps else None, stage_events)
-        return (out, tap) if taps else out
-
-    def _chunk(self, img, bufs, out, tap, stage_events):
-        n, L, W, H, D = img.shape[0], self.tokens, self.width, self.heads, self.head_dim
-        M, eps = n * L, self.ln_eps
-
-        def staged(label, fn):
-            if stage_events is None:
-                return fn()
-            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record()
-            r = fn()
-            end.record()
-            stage_events.append((label, start, end))
-            return r
-
-        x, y, qkv, hid = bufs["x"][:M], bufs["y"][:M], bufs["qkv"][:M], bufs["hid"][:M]
-        rows, pe, pooled = bufs["rows"][:n * (L - 1)], bufs["pe"][:n * (L - 1)], bufs["pooled"][:n]
-        yw, hw = y[:, :W], hid[:, :self.mlp]
-        staged("patch_rows", lambda: ops.vit_patches_f32(img, self.patch, self.mean_std, self.Kp, out=rows))
-        staged("gemm_patch", lambda: ops.gemm(rows, self.patch_w, pe, bias=self.patch_b))
-        if self.ln_pre is not None:
-            tokens = qkv.view(-1)[:M * W].view(M, W)      # q|k|v is free until block 0: the stream starts at norm_pre's output
-            staged("tokens", lambda: ops.vit_tokens(pe, self.cls, self.pos, out=tokens))
-            staged("layernorm", lambda: ops.layernorm_wide(tokens, *self.ln_pre, eps, out=x))
-        else:
-            staged("tokens", lambda: ops.vit_tokens(pe, self.cls, self.pos, out=x))
-        if tap is not None:
-            tap["embed"].copy_(x.view(n, L, W))
-        for i, blk in enumerate(self.blocks):
-            staged("layernorm", lambda: ops.layernorm_wide(x, *blk.ln_1, eps, out=yw))
-            staged("gemm_qkv", lambda: ops.gemm(y, blk.in_proj[0], qkv, bias=blk.in_proj[1]))
-            staged("attention", lambda: ops.attention_tok(qkv, n, L, H, D, D ** -0.5, out=yw))
-            staged("gemm_proj", lambda: ops.gemm(y, blk.out_proj[0], x, bias=blk.out_proj[1], residual=x))
-            staged("layernorm", lambda: ops.layernorm_wide(x, *blk.ln_2, eps, out=yw))
-            staged("gemm_fc1", lambda: ops.gemm(y, blk.c_fc[0], hw, bias=blk.c_fc[1], act=self.act_code))
-            staged("gemm_fc2", lambda: ops.gemm(hid, blk.c_proj[0], x, bias=blk.c_proj[1], residual=x))
-            if tap is not None and i == 0:
-                tap["block0"].copy_(x.view(n, L, W))
-        if tap is not None:
-            tap["last_block"].copy_(x.view(n, L, W))
-        cls_rows = x.view(n, L, W)[:, 0]                  # the class rows: a [n, W] view with leading dimension L * W
-        if self.feature == "cls_prenorm":
-            out.copy_(cls_rows)
-        elif self.feature == "cls":
-            staged("layernorm", lambda: ops.layernorm_wide(cls_rows, *self.ln_post, eps, out=out))
-        else:
-            staged("layernorm", lambda: ops.layernorm_wide(cls_rows, *self.ln_post, eps, out=pooled[:, :W]))
-            staged("gemm_head", lambda: ops.gemm(pooled, self.proj_t, out))
-        if tap is not None:
-            tap["cls_row"].copy_(out if self.feature != "embedding" else pooled[:, :W])
-
 
 # ------------------------------------------------------------------------------------------- the metric
 def normalize_embedding(e: torch.Tensor) -> torch.Tensor:
@@ -566,14 +240,11 @@ def build_ensemble(dino, clip, open_clip, device="cuda", lora=None, lora_alpha: 
     eps 1e-6, feature `dino_feature`), clip_vitb16 (open_clip layout, QuickGELU) and open_clip_vitb16 (open_clip layout, GELU),
     the latter two with OpenAI's mean / std and feature "embedding".  lora: an adapter state dict or path holding the adapters of
     every tower it names; it is merged into the tower whose keys it matches (lora_alpha has no default)."""
-    states = []
-    for s in (dino, clip, open_clip):
-        states.append(_load_file(os.fspath(s)) if isinstance(s, (str, os.PathLike)) else s)
+    states = [state_of(s, "build_ensemble") for s in (dino, clip, open_clip)]
     if lora is not None:
         if lora_alpha is None:
             raise M324Error("build_ensemble: lora needs lora_alpha (the adapter's adapter_config.json has it)")
-        adapter = _load_file(os.fspath(lora)) if isinstance(lora, (str, os.PathLike)) else lora
-        states[0] = merge_lora(states[0], adapter, lora_alpha)
+        states[0] = merge_lora(states[0], state_of(lora, "build_ensemble"), lora_alpha)
     towers = (VitTower(load_vit_weights(states[0], "dino"), device, "gelu", DINO_LN_EPS, IMAGENET_MEAN, IMAGENET_STD, dino_feature),
               VitTower(load_vit_weights(states[1], "open_clip"), device, "quick_gelu", CLIP_LN_EPS, OPENAI_MEAN, OPENAI_STD, "embedding"),
               VitTower(load_vit_weights(states[2], "open_clip"), device, "gelu", CLIP_LN_EPS, OPENAI_MEAN, OPENAI_STD, "embedding"))

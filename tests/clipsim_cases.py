@@ -1,25 +1,23 @@
 """Cases, oracle, bounds and gate of the CLIP similarity tests (tests/test_clipsim_cpu.py, tests/test_clipsim_gpu.py,
 tests/golden/make_clip_band.py).  Derivations: tests/ERROR_BOUNDS_CLIP.md.
 
-The oracle is a torch CPU model of open_clip's VisionTransformer at a chosen precision, written from its definition: F.conv2d
-with stride = patch, F.layer_norm with eps 1e-5, explicit q / k / v slices of the in-projection, softmax(q k^T D^-0.5) v per
-head, F.gelu, the class token through ln_post and `pooled @ proj`.  Six faults can be planted into it; the CPU tests require the
-gate to see each.  The preprocessing model is PIL's own resize on the host.
+The oracle is the tower model of tests/vit_cases.py on the preprocessed bytes / 255, as open_clip's VisionTransformer (GELU, eps
+1e-5, the embedding), with the taps under ClipVision's names.  Six faults can be planted into it; the CPU tests require the gate
+to see each.  The preprocessing model is PIL's own resize on the host.
 """
 import math
 import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from motion324_amd import clipsim as C
 
+import vit_cases as V
 from error_bounds import EXP2, U32
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_band.npz")
 WEIGHT_SEED = 324
-GATE_FACTOR = 8.0           # times the recorded deviation of the fp32 CPU run; the reason is in tests/ERROR_BOUNDS_FVD.md
 FAULTS = ("quick_gelu", "scale_64", "kv_swapped", "pos_shifted_one_row", "ln_post_skipped", "ln_eps_1e-6")
 TAPS = C.TAPS
 KEYS = TAPS + ("features",)
@@ -107,72 +105,17 @@ def resample_pass(img, coef, bounds, axis):
     return np.moveaxis(out, 0, axis).astype(np.uint8)
 
 
-def normalised(img_u8, dtype, mean=C.OPENAI_MEAN, std=C.OPENAI_STD):
-    """[n,3,S,S] of preprocessed bytes by the formula of the patch kernel: (v / 255 - mean) / std, each operation in fp32 (so
-    that every precision of the oracle starts from the input the kernel sees)"""
-    x = torch.from_numpy(np.ascontiguousarray(img_u8)).permute(0, 3, 1, 2).to(torch.float32)
-    m = torch.tensor(mean, dtype=torch.float32).reshape(1, 3, 1, 1)
-    s = torch.tensor(std, dtype=torch.float32).reshape(1, 3, 1, 1)
-    return ((x / 255.0 - m) / s).to(dtype).contiguous()
-
-
 def patch_rows_model(img_u8, patch, Kp, mean=C.OPENAI_MEAN, std=C.OPENAI_STD):
-    """fp32 [n * g * g, Kp]: the host formula of m324_vit_patches"""
-    x = normalised(img_u8, torch.float32, mean, std)
-    n, _, S, _ = x.shape
-    g = S // patch
-    rows = x.reshape(n, 3, g, patch, g, patch).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, 3 * patch * patch)
-    out = torch.zeros((n * g * g, Kp), dtype=torch.float32)
-    out[:, :3 * patch * patch] = rows
-    return out
+    """fp32 [n * g * g, Kp]: the host formula of m324_vit_patches, (v / 255 - mean) / std with each operation in fp32"""
+    return V.patch_rows_model(torch.from_numpy(bytes_to_float(img_u8)), patch, Kp, mean, std)
 
 
 # ------------------------------------------------------------------------------------------- the oracle
 def oracle(img_u8, state, heads, dtype=torch.float64, fault=None):
     """{tap: numpy float64, "features": [n, E]} of preprocessed bytes uint8 [n,S,S,3]; taps as ClipVision.features(taps=True)"""
     assert fault is None or fault in FAULTS, fault
-    sd = {k: v.to(dtype) for k, v in state.items()}
-    eps = 1e-6 if fault == "ln_eps_1e-6" else 1e-5
-    out = {}
-    with torch.no_grad():
-        x = normalised(img_u8, dtype)
-        W, patch = sd["conv1.weight"].shape[0], sd["conv1.weight"].shape[2]
-        x = F.conv2d(x, sd["conv1.weight"], stride=patch)                       # [n, W, g, g]
-        n = x.shape[0]
-        x = x.reshape(n, W, -1).permute(0, 2, 1)
-        x = torch.cat([sd["class_embedding"].reshape(1, 1, W).expand(n, 1, W), x], 1)
-        pos = sd["positional_embedding"]
-        x = x + (torch.roll(pos, 1, 0) if fault == "pos_shifted_one_row" else pos)
-        L = x.shape[1]
-        x = F.layer_norm(x, (W,), sd["ln_pre.weight"], sd["ln_pre.bias"], eps)
-        out["ln_pre"] = x.double().numpy()
-        D = W // heads
-        scale = 64 ** -0.5 if fault == "scale_64" else D ** -0.5
-        i = 0
-        while f"transformer.resblocks.{i}.ln_1.weight" in sd:
-            b = f"transformer.resblocks.{i}."
-            y = F.layer_norm(x, (W,), sd[b + "ln_1.weight"], sd[b + "ln_1.bias"], eps)
-            qkv = y @ sd[b + "attn.in_proj_weight"].t() + sd[b + "attn.in_proj_bias"]
-            q, k, v = (qkv[..., j * W:(j + 1) * W].reshape(n, L, heads, D).permute(0, 2, 1, 3) for j in range(3))
-            if fault == "kv_swapped":
-                k, v = v, k
-            a = torch.softmax(q @ k.transpose(2, 3) * scale, dim=-1) @ v
-            a = a.permute(0, 2, 1, 3).reshape(n, L, W)
-            x = x + a @ sd[b + "attn.out_proj.weight"].t() + sd[b + "attn.out_proj.bias"]
-            y = F.layer_norm(x, (W,), sd[b + "ln_2.weight"], sd[b + "ln_2.bias"], eps)
-            h = y @ sd[b + "mlp.c_fc.weight"].t() + sd[b + "mlp.c_fc.bias"]
-            h = h * torch.sigmoid(1.702 * h) if fault == "quick_gelu" else F.gelu(h)
-            x = x + h @ sd[b + "mlp.c_proj.weight"].t() + sd[b + "mlp.c_proj.bias"]
-            if i == 0:
-                out["block0"] = x.double().numpy()
-            i += 1
-        out["last_block"] = x.double().numpy()
-        pooled = x[:, 0]
-        if fault != "ln_post_skipped":
-            pooled = F.layer_norm(pooled, (W,), sd["ln_post.weight"], sd["ln_post.bias"], eps)
-        out["ln_post"] = pooled.double().numpy()
-        out["features"] = (pooled @ sd["proj"]).double().numpy()
-    return out
+    out = V.oracle(torch.from_numpy(bytes_to_float(img_u8)), state, heads, dtype=dtype, fault=fault)
+    return {**{mine: out[shared] for mine, shared in zip(TAPS, V.TAPS)}, "features": out["features"]}
 
 
 def case_oracle(name, dtype=torch.float64, fault=None):
@@ -185,51 +128,20 @@ def cosine_model(fa, fb):
 
 
 # ------------------------------------------------------------------------------------------- the band and the gate
-def rms(a):
-    return float(np.sqrt(np.mean(np.square(np.asarray(a, dtype=np.float64)))))
-
-
-def deviation(values, ref):
-    """the largest |values - ref| relative to the RMS of ref"""
-    return float(np.abs(np.asarray(values, dtype=np.float64) - ref).max() / rms(ref))
-
-
-SAMPLE = 4096               # elements of a tap the golden file keeps (a committed file stays small); the features are kept whole
+rms, deviation, SAMPLE = V.rms, V.deviation, V.SAMPLE
 
 
 def sample_index(name, key, size):
-    if size <= SAMPLE:
-        return np.arange(size)
-    rng = np.random.default_rng(9000 + 10 * list(CASES).index(name) + KEYS.index(key))
-    return np.sort(rng.choice(size, SAMPLE, replace=False))
-
-
-class Entry:
-    """one golden record: the fp64 values at the sampled elements, the RMS of the whole tap, and the band, the fp32 CPU run's
-    largest deviation over the WHOLE tap relative to that RMS"""
-
-    def __init__(self, z, name, key):
-        p = f"{name}.{key}."
-        self.ref, self.size, self.rms, self.band = z[p + "ref"], int(z[p + "size"]), float(z[p + "rms"]), float(z[p + "band"])
-        self.index = sample_index(name, key, self.size)
-
-    def deviation(self, values):
-        v = np.asarray(values, dtype=np.float64).reshape(-1)
-        assert v.size == self.size, (v.size, self.size)
-        return float(np.abs(v[self.index] - self.ref).max() / self.rms)
+    return V.sample_index(9000, list(CASES).index(name), KEYS.index(key), size)
 
 
 def golden():
     """{case: {key: Entry}} from tests/golden/clip_band.npz"""
-    if "golden" not in _STATE:
-        z = np.load(GOLDEN)
-        _STATE["golden"] = {name: {k: Entry(z, name, k) for k in KEYS} for name in CASES}
-    return _STATE["golden"]
+    return V.golden(GOLDEN, CASES, KEYS, 9000)
 
 
 def gate(name, key):
-    """the largest deviation allowed for a tap (or the features) of a case: GATE_FACTOR times the recorded band"""
-    return GATE_FACTOR * golden()[name][key].band
+    return V.gate(golden(), name, key)
 
 
 def cosine_bound(fa, fb, dev_abs):

@@ -1,10 +1,7 @@
 """Cases, oracle, bounds and gate of the DreamSim tests (tests/test_dreamsim_cpu.py, tests/test_dreamsim_gpu.py,
 tests/golden/make_dreamsim_band.py).  Derivations: tests/ERROR_BOUNDS_DREAMSIM.md.
 
-The oracle is a torch CPU model of a ViT image tower at a chosen precision, written from the definitions of timm's and
-open_clip's VisionTransformer: F.conv2d with stride = patch (with the bias the DINO layout has), the class token and positions,
-an optional LayerNorm in front of the blocks, explicit q / k / v slices of the fused projection, softmax(q k^T D^-0.5) v per head,
-F.gelu or x sigmoid(1.702 x), and one of three class features.  The resize model is the float64 matrix product under
+The oracle is the tower model of tests/vit_cases.py.  The resize model is the float64 matrix product under
 dreamsim.resize_matrix, itself checked against F.interpolate.  Faults can be planted; the CPU tests require the gate to see each.
 """
 import math
@@ -12,17 +9,16 @@ import os
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from motion324_amd import dreamsim as D
-from motion324_amd.clipsim import OPENAI_MEAN, OPENAI_STD, synth_clip_state_dict
+from motion324_amd.vit import OPENAI_MEAN, OPENAI_STD, synth_clip_state_dict
 
 import clipsim_cases as CC
+import vit_cases as V
 from error_bounds import EXP2, TINY32, U32
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dreamsim_band.npz")
 WEIGHT_SEED = 3240
-GATE_FACTOR = 8.0           # times the recorded deviation of the fp32 CPU run; the reason is in tests/ERROR_BOUNDS_FVD.md
 TAPS = D.TAPS
 KEYS = TAPS + ("features",)
 RESIZE_SHAPES = ((512, 512, 224, 224), (37, 53, 224, 224), (96, 130, 32, 48), (225, 300, 224, 224), (64, 64, 64, 64), (5, 7, 3, 2))
@@ -99,93 +95,7 @@ def resample_pass(x, weights, first, axis):
 
 
 # ------------------------------------------------------------------------------------------- the oracle
-def normalised(img, dtype, mean, std):
-    """[n,3,S,S] by the formula of the patch kernel: (x - mean) / std, both operations in fp32 (every precision of the oracle
-    starts from the input the kernel sees)"""
-    m = torch.tensor(mean, dtype=torch.float32).reshape(1, 3, 1, 1)
-    s = torch.tensor(std, dtype=torch.float32).reshape(1, 3, 1, 1)
-    return ((img.to(torch.float32) - m) / s).to(dtype).contiguous()
-
-
-def patch_rows_model(img, patch, Kp, mean, std):
-    """fp32 [n * g * g, Kp]: the host formula of m324_vit_patches_f32"""
-    x = normalised(img, torch.float32, mean, std)
-    n, _, S, _ = x.shape
-    g = S // patch
-    rows = x.reshape(n, 3, g, patch, g, patch).permute(0, 2, 4, 1, 3, 5).reshape(n * g * g, 3 * patch * patch)
-    out = torch.zeros((n * g * g, Kp), dtype=torch.float32)
-    out[:, :3 * patch * patch] = rows
-    return out
-
-
-_OPEN_CLIP_NAMES = {"patch_w": "conv1.weight", "patch_b": None, "cls": "class_embedding", "pos": "positional_embedding", "ln_pre": "ln_pre",
-                    "block": "transformer.resblocks.{}.", "ln_1": "ln_1", "qkv_w": "attn.in_proj_weight", "qkv_b": "attn.in_proj_bias",
-                    "proj": "attn.out_proj", "ln_2": "ln_2", "fc1": "mlp.c_fc", "fc2": "mlp.c_proj", "norm": "ln_post"}
-_DINO_NAMES = {"patch_w": "patch_embed.proj.weight", "patch_b": "patch_embed.proj.bias", "cls": "cls_token", "pos": "pos_embed",
-               "ln_pre": "norm_pre", "block": "blocks.{}.", "ln_1": "norm1", "qkv_w": "attn.qkv.weight", "qkv_b": "attn.qkv.bias",
-               "proj": "attn.proj", "ln_2": "norm2", "fc1": "mlp.fc1", "fc2": "mlp.fc2", "norm": "norm"}
-
-
-def oracle(img, state, heads, *, act="gelu", ln_eps=1e-5, mean=OPENAI_MEAN, std=OPENAI_STD, feature="embedding", dtype=torch.float64,
-           fault=None, lora=None):
-    """{tap: numpy float64, "features": [n, E]} of fp32 planar images [n,3,S,S]; taps as VitTower.features(taps=True).
-    lora = (adapter state dict, alpha): the adapters of attn.qkv applied UNMERGED, x W^T + (alpha / r) (x A^T) B^T."""
-    assert fault in (None, "erf_gelu", "ln_eps_1e-5", "patch_bias_dropped", "ln_pre_applied", "openai_mean_std"), fault
-    names = _DINO_NAMES if "patch_embed.proj.weight" in state else _OPEN_CLIP_NAMES
-    sd = {k: torch.as_tensor(v).to(dtype) for k, v in state.items()}
-    eps = 1e-5 if fault == "ln_eps_1e-5" else ln_eps
-    if fault == "openai_mean_std":
-        mean, std = OPENAI_MEAN, OPENAI_STD
-    if fault == "erf_gelu":
-        act = "gelu"
-
-    def ln(x, name):
-        return F.layer_norm(x, (x.shape[-1],), sd[name + ".weight"], sd[name + ".bias"], eps)
-
-    out = {}
-    with torch.no_grad():
-        x = normalised(img, dtype, mean, std)
-        conv = sd[names["patch_w"]]
-        W, patch = conv.shape[0], conv.shape[2]
-        bias = sd[names["patch_b"]] if names["patch_b"] and fault != "patch_bias_dropped" else None
-        x = F.conv2d(x, conv, bias, stride=patch)
-        n = x.shape[0]
-        x = x.reshape(n, W, -1).permute(0, 2, 1)
-        x = torch.cat([sd[names["cls"]].reshape(1, 1, W).expand(n, 1, W), x], 1) + sd[names["pos"]].reshape(1, -1, W)
-        L = x.shape[1]
-        if names["ln_pre"] + ".weight" in sd:
-            x = ln(x, names["ln_pre"])
-        elif fault == "ln_pre_applied":
-            x = F.layer_norm(x, (W,), None, None, eps)
-        out["embed"] = x.double().numpy()
-        Dh = W // heads
-        i = 0
-        while names["block"].format(i) + names["ln_1"] + ".weight" in sd:
-            b = names["block"].format(i)
-            y = ln(x, b + names["ln_1"])
-            qkv = y @ sd[b + names["qkv_w"]].t() + sd[b + names["qkv_b"]]
-            if lora is not None:
-                adapter, alpha = lora
-                A, B = (torch.as_tensor(adapter[f"base_model.model.{b}attn.qkv.lora_{s}.default.weight"]).to(dtype) for s in "AB")
-                qkv = qkv + (alpha / A.shape[0]) * ((y @ A.t()) @ B.t())
-            q, k, v = (qkv[..., j * W:(j + 1) * W].reshape(n, L, heads, Dh).permute(0, 2, 1, 3) for j in range(3))
-            a = torch.softmax(q @ k.transpose(2, 3) * Dh ** -0.5, dim=-1) @ v
-            a = a.permute(0, 2, 1, 3).reshape(n, L, W)
-            x = x + a @ sd[b + names["proj"] + ".weight"].t() + sd[b + names["proj"] + ".bias"]
-            y = ln(x, b + names["ln_2"])
-            h = y @ sd[b + names["fc1"] + ".weight"].t() + sd[b + names["fc1"] + ".bias"]
-            h = h * torch.sigmoid(1.702 * h) if act == "quick_gelu" else F.gelu(h)
-            x = x + h @ sd[b + names["fc2"] + ".weight"].t() + sd[b + names["fc2"] + ".bias"]
-            if i == 0:
-                out["block0"] = x.double().numpy()
-            i += 1
-        out["last_block"] = x.double().numpy()
-        row = x[:, 0]
-        if feature != "cls_prenorm":
-            row = ln(row, names["norm"])
-        out["cls_row"] = row.double().numpy()
-        out["features"] = (row @ sd["proj"]).double().numpy() if feature == "embedding" else out["cls_row"]
-    return out
+oracle, patch_rows_model = V.oracle, V.patch_rows_model
 
 
 def case_oracle(name, dtype=torch.float64, fault=None, img=None):
@@ -253,34 +163,20 @@ def distance_features(frames, dtype=torch.float64, antialias=True):
 
 
 # ------------------------------------------------------------------------------------------- the band and the gate
-rms, deviation, SAMPLE = CC.rms, CC.deviation, CC.SAMPLE
+rms, deviation, SAMPLE = V.rms, V.deviation, V.SAMPLE
 
 
 def sample_index(name, key, size):
-    if size <= SAMPLE:
-        return np.arange(size)
-    rng = np.random.default_rng(19000 + 10 * list(CASES).index(name) + KEYS.index(key))
-    return np.sort(rng.choice(size, SAMPLE, replace=False))
-
-
-class Entry(CC.Entry):
-    def __init__(self, z, name, key):
-        p = f"{name}.{key}."
-        self.ref, self.size, self.rms, self.band = z[p + "ref"], int(z[p + "size"]), float(z[p + "rms"]), float(z[p + "band"])
-        self.index = sample_index(name, key, self.size)
+    return V.sample_index(19000, list(CASES).index(name), KEYS.index(key), size)
 
 
 def golden():
     """{case: {key: Entry}} from tests/golden/dreamsim_band.npz"""
-    if "golden" not in _STATE:
-        z = np.load(GOLDEN)
-        _STATE["golden"] = {name: {k: Entry(z, name, k) for k in KEYS} for name in CASES}
-    return _STATE["golden"]
+    return V.golden(GOLDEN, CASES, KEYS, 19000)
 
 
 def gate(name, key):
-    """the largest deviation allowed for a tap (or the features) of a case: GATE_FACTOR times the recorded band"""
-    return GATE_FACTOR * golden()[name][key].band
+    return V.gate(golden(), name, key)
 
 
 # ------------------------------------------------------------------------------------------- kernel bounds

@@ -1,8 +1,8 @@
 """Times the CLIP similarity of two device-resident clips under seeded ViT-bigG-14-sized weights:
 python tools/clipsim_time.py [--frames 32 --size 512 --layers 48]
 
-Device events around the call, one warm-up, the median of 5 with min and max; the shares of preprocessing, patch embedding,
-LayerNorms, the four GEMM roles, attention and the head from events inside one call; the tower's achieved TFLOP/s against the
+Device events around the call, one warm-up, the median of 5 with min and max; the shares of preprocessing, the patch rows and
+their GEMM, the token assembly, LayerNorms, the four GEMM roles, attention and the head GEMM from events inside one call; the tower's achieved TFLOP/s against the
 fp32 matrix peak (157.3 TFLOP/s); m324_attention_tok alone at B H = 1024, L = 257, D = 104; and, as a yardstick in the same
 run, the block's four GEMMs alone at the tower's shapes -- tower / GEMMs-alone is what the new kernels and launches cost on top.
 The weights are generated on the device (7.4 GB at 48 layers).  Prints markdown tables and one JSON line.
@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from motion324_amd import clipsim as C  # noqa: E402
 from motion324_amd import lib, ops  # noqa: E402
+from motion324_amd.vit import VitBlock, VitWeights  # noqa: E402
 
 PEAK_TFLOPS = 157.3
 REPEATS = 5
@@ -41,7 +42,7 @@ def timed(fn):
 
 
 def device_weights(layers, dev, seed=0):
-    """a ClipVisionWeights of bigG's sizes made on the device, of synth_clip_state_dict's scales"""
+    """a VitWeights of bigG's sizes made on the device, of synth_clip_state_dict's scales"""
     g = torch.Generator(device=dev).manual_seed(seed)
 
     def randn(*shape, scale=1.0):
@@ -58,12 +59,14 @@ def device_weights(layers, dev, seed=0):
     for _ in range(layers):
         w_in = randn(3 * WIDTH, WIDTH, scale=1.0 / math.sqrt(WIDTH))
         w_in[:2 * WIDTH] *= 2.0
-        blocks.append(C.ClipBlock(ln(), (w_in, randn(3 * WIDTH, scale=0.05)),
-                                  (randn(WIDTH, WIDTH, scale=1.0 / math.sqrt(WIDTH)), randn(WIDTH, scale=0.05)), ln(),
-                                  (randn(MLP, WIDTH, scale=1.0 / math.sqrt(WIDTH)), randn(MLP, scale=0.05)),
-                                  (randn(WIDTH, MLP, scale=1.0 / math.sqrt(MLP)), randn(WIDTH, scale=0.05))))
-    return C.ClipVisionWeights(WIDTH, HEADS, layers, MLP, PATCH, IMAGE, L, EMBED, patch_w, randn(WIDTH, scale=0.1), randn(L, WIDTH, scale=0.1),
-                               ln(), tuple(blocks), ln(), randn(EMBED, WIDTH, scale=1.0 / math.sqrt(WIDTH)))
+        blocks.append(VitBlock(ln(), (w_in, randn(3 * WIDTH, scale=0.05)),
+                               (randn(WIDTH, WIDTH, scale=1.0 / math.sqrt(WIDTH)), randn(WIDTH, scale=0.05)), ln(),
+                               (randn(MLP, WIDTH, scale=1.0 / math.sqrt(WIDTH)), randn(MLP, scale=0.05)),
+                               (randn(WIDTH, MLP, scale=1.0 / math.sqrt(MLP)), randn(WIDTH, scale=0.05))))
+    # keyword arguments are evaluated in the order written: the order of draws is the one this tool has always had
+    return VitWeights(width=WIDTH, heads=HEADS, layers=layers, mlp=MLP, patch=PATCH, image=IMAGE, tokens=L, embed=EMBED, patch_w=patch_w,
+                      patch_b=None, cls=randn(WIDTH, scale=0.1), pos=randn(L, WIDTH, scale=0.1), ln_pre=ln(), blocks=tuple(blocks),
+                      ln_post=ln(), proj_t=randn(EMBED, WIDTH, scale=1.0 / math.sqrt(WIDTH)))
 
 
 def main(argv=None):
@@ -82,7 +85,7 @@ def main(argv=None):
     b = torch.randint(0, 256, (T, S, S, 3), generator=g, dtype=torch.uint8).to(dev)
     n, L, W, D = 2 * T, model.tokens, WIDTH, WIDTH // HEADS
     M = n * L
-    gemm_flop = {"gemm_in_proj": 2.0 * M * W * 3 * W, "gemm_out_proj": 2.0 * M * W * W, "gemm_c_fc": 2.0 * M * W * MLP, "gemm_c_proj": 2.0 * M * MLP * W}
+    gemm_flop = {"gemm_qkv": 2.0 * M * W * 3 * W, "gemm_proj": 2.0 * M * W * W, "gemm_fc1": 2.0 * M * W * MLP, "gemm_fc2": 2.0 * M * MLP * W}
     attn_flop = 4.0 * n * HEADS * L * L * D
     tower_flop = layers * (sum(gemm_flop.values()) + attn_flop) + 2.0 * n * (L - 1) * model.Kp * W + 2.0 * n * W * EMBED
     result = {"device": name, "cus": cus, "frames": T, "size": S, "layers": layers, "images": n, "tower_tflop": tower_flop / 1e12,
@@ -104,7 +107,7 @@ def main(argv=None):
     total = sum(spent.values())
     result["stages_ms"] = spent
     print("\nshares (events inside one call, around every launch):\n\n| part | ms | share | TFLOP/s |\n|---|---|---|---|")
-    for label in ("preprocess", "patch_embed", "layernorm", "gemm_in_proj", "attention", "gemm_out_proj", "gemm_c_fc", "gemm_c_proj", "head"):
+    for label in ("preprocess", "patch_rows", "gemm_patch", "tokens", "layernorm", "gemm_qkv", "attention", "gemm_proj", "gemm_fc1", "gemm_fc2", "gemm_head"):
         fl = layers * gemm_flop[label] if label in gemm_flop else (layers * attn_flop if label == "attention" else 0.0)
         rate = f"{fl / spent[label] / 1e9:.1f}" if fl else "-"
         print(f"| {label} | {spent[label]:.2f} | {100 * spent[label] / total:.1f} % | {rate} |")
